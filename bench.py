@@ -26,7 +26,11 @@ is that one solve's GMRES iterations per second at every N):
   strong               --global-rows R: one R-row BAND matrix split over the
                        N ranks (R = 1e7 is the north star's 100M-nnz matrix).
 
-Also reported, at every N from rank 0: the roofline of the dominant kernel --
+A plain run sets up, warms up, times --steps cycles and prints the result
+line; --dump-outputs DIR also writes the timed solve's result (dump_outputs).
+
+With --full also reported, at every N from rank 0 (each takes runs of its own
+after the timed steps): the roofline of the dominant kernel --
 the Arnoldi SpMV as the cycle runs it (Givens folded on one GPU), each launch
 timed by its own kernel events -- on the bytes its storage moves, against the
 8 TB/s spec and the GPU's measured streaming peak (mpg_bw_probe, 2 GiB), with
@@ -107,7 +111,7 @@ ROCPROF_STATS = "bench_kernel_stats.rocprof"
 def rocprof_avg_ms(profile_dir: Path, kernel: str):
     """Mean duration (ms) over all launches of `kernel` (every template
     instance) in the committed rocprofv3 --kernel-trace --stats summary of
-    `bench.py --steps 10 --no-cpu-baseline --hbm-rows 0 --surface-cycles 0`
+    `bench.py --full --steps 10 --no-cpu-baseline --hbm-rows 0 --surface-cycles 0`
     (profiles/bench_kernel_stats.rocprof: the CSV, renamed so it travels with the tree), None when absent:
     the CP's timestamps of each dispatch, which rocprof reports, set beside
     the live wave-stamp time."""
@@ -478,13 +482,48 @@ def dry_run_line(args) -> None:
     print(json.dumps(line), flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_X_ROWS = 4 << 20      # rows of x written whole; a longer x is sampled down to this many
+DUMP_HISTORY = 1 << 19     # the last entries kept of a longer per-cycle or per-step history
+
+
+def dump_outputs(eng, args, world: int, rank: int, dump_dir: Path) -> None:
+    """--dump-outputs: what the timed path's caller receives after the last
+    timed cycle (mpg_engine_report: the solve as mpg_solve reports it), as
+    <name>.npy in float64 -- x (this rank's rows of the iterate; past
+    DUMP_X_ROWS rows a fixed seeded sample of them, ascending), the per-cycle
+    true-residual norm, normalisation and beta, the per-step residual
+    estimates, and [resNorm, errNorm]. At N > 1 every rank writes its x
+    (x_rank<q>.npy; the report is collective) and rank 0 the histories. The
+    inputs are seeded, so two builds run with the same arguments are compared
+    file for file."""
+    cycles = args.warmup + args.steps + 11
+    res = eng.report(cycle_cap=cycles, step_cap=cycles * args.rlen)
+    x = res.x
+    if x.size > DUMP_X_ROWS:
+        x = x[np.sort(np.random.default_rng(0).choice(x.size, DUMP_X_ROWS, replace=False))]
+    arrays = {"x" if world == 1 else f"x_rank{rank}": x}
+    if rank == 0:
+        for k in ("cyc_r_norm", "cyc_normalization", "cyc_beta", "step_res"):
+            arrays[k] = getattr(res, k)[-DUMP_HISTORY:]
+        arrays["final_norms"] = np.array([res.res_norm, res.err_norm])
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    dump_dir.mkdir(parents=True, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(dump_dir / f"{k}.npy", v)
+    log(f"[bench] rank {rank}: wrote {sorted(arrays)} ({total / 1e6:.1f} MB) to {dump_dir}")
+
+
 def measure(mpg, torch, dist, args, world, rank, local_rank, n, strong, keep=False) -> dict:
     """One row-partitioned BAND solve of n global rows (strong: split evenly
     over the ranks; weak: args.n_local rows per rank): build this rank's row
     block and engine, run the warm-up cycles, then time exactly args.steps
     restart cycles between a barrier + device synchronise on both sides; the
     time is the max over ranks. keep=True returns the engine (open) and the
-    local problem for the roofline / surface / CPU legs."""
+    local problem for the roofline / surface / CPU legs, and is the headline
+    solve: --dump-outputs writes its result."""
     starts = [n * q // world for q in range(world + 1)] if strong else [q * args.n_local for q in range(world + 1)]
     r0, r1 = starts[rank], starts[rank + 1]
     t0 = time.time()
@@ -543,6 +582,8 @@ def measure(mpg, torch, dist, args, world, rank, local_rank, n, strong, keep=Fal
         f"{elapsed:.4f}s -> {rate:.1f} it/s; communicator ranks {comm_ranks}")
     out = {"r0": r0, "r1": r1, "rate": rate, "elapsed": elapsed, "comm_ranks": comm_ranks, "opts": opts}
     if keep:
+        if args.dump_outputs:
+            dump_outputs(eng, args, world, rank, Path(args.dump_outputs))
         out.update(engine=eng, A=A, b=b, xt=xt)
     else:
         out["spmv_ms"] = spmv_roofline(eng, args.roofline_cycles)["avg_launch_ms"]
@@ -596,6 +637,13 @@ def main():
                          "star's 100M-nnz strong-scaling case; 0: skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="start the ranks and report what each would run; no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the SpMV / phase "
+                         "rooflines and the streaming peak, the HBM-scale SpMV, the operator surface, the N > 1 "
+                         "strong-scaling case and the CPU baseline (a plain run leaves these fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the headline solve's result (x, residual histories) as "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -610,7 +658,7 @@ def main():
     # the CPU facts before anything binds this thread (libgomp pins the
     # initial thread to one place under OMP_PROC_BIND)
     global _CPU_INFO
-    _CPU_INFO = cpu_info()
+    _CPU_INFO = cpu_info() if args.full else None
     # the CPU baseline's OpenMP placement (automated.py:13-15); libgomp reads
     # these when it is first loaded, which importing torch does
     os.environ.setdefault("OMP_PROC_BIND", "spread")
@@ -658,11 +706,14 @@ def main():
     value = solve_rate  # the one solve's iterations per second, at every N
     ms_per_step = 1e3 * elapsed / args.steps
 
+    layout = eng.spmv_layout()
+    # A plain run is done measuring here. Everything below takes runs of its
+    # own and belongs to --full; without it those fields of the line are null.
     # roofline of the dominant kernel: the Arnoldi SpMV as the cycle runs it
-    sp = spmv_roofline(eng, args.roofline_cycles)
+    sp = spmv_roofline(eng, args.roofline_cycles) if args.full else None
     pmc = pmc_traffic(REPO / "profiles")
     phases = (phase_roofline(eng, args.rlen, args.roofline_cycles, pmc)
-              if args.orth == "cgs" and world == 1 and sp["timing"] == "dup" else None)
+              if sp and args.orth == "cgs" and world == 1 and sp["timing"] == "dup" else None)
     # the whole CGS Arnoldi iteration on the same footing: the SpMV's storage
     # bytes + the panel dots and the CGS update at the cycle's mean k (the
     # once-per-cycle prologue and solution update are left out, so this
@@ -670,17 +721,18 @@ def main():
     iter_bytes = (eng.phase_bytes("spmv_storage") + eng.phase_bytes("dots") + eng.phase_bytes("cgs_update")
                   if args.orth == "cgs" else None)
     eng.close()
-    log(f"[bench] rank {rank} {sp['kernel']} in-cycle {sp['avg_launch_ms'] * 1e3:.2f} us/launch over {sp['launches']} "
-        f"launches: {sp['achieved_gbs']:.0f} GB/s on its storage bytes, {sp['csr_equiv_gbs']:.0f} GB/s "
-        f"CSR-equivalent; {sp['layout']}")
-    per_rank_ms = [sp["avg_launch_ms"]]
-    if dist:
+    if sp:
+        log(f"[bench] rank {rank} {sp['kernel']} in-cycle {sp['avg_launch_ms'] * 1e3:.2f} us/launch over "
+            f"{sp['launches']} launches: {sp['achieved_gbs']:.0f} GB/s on its storage bytes, "
+            f"{sp['csr_equiv_gbs']:.0f} GB/s CSR-equivalent; {sp['layout']}")
+    per_rank_ms = [sp["avg_launch_ms"]] if sp else None
+    if dist and sp:
         per_rank_ms = [None] * world
         dist.all_gather_object(per_rank_ms, sp["avg_launch_ms"])
     # N > 1: the north star's 100M-nnz strong-scaling case beside the default
     # weak one (one 1e7-row BAND matrix split over the ranks)
     strong100 = None
-    if world > 1 and args.strong_rows > 0 and not (strong and n == args.strong_rows):
+    if args.full and world > 1 and args.strong_rows > 0 and not (strong and n == args.strong_rows):
         sm = measure(mpg, torch, dist, args, world, rank, local_rank, args.strong_rows, True)
         sp_ms = [None] * world
         dist.all_gather_object(sp_ms, sm["spmv_ms"])
@@ -693,11 +745,11 @@ def main():
                      "rows_per_gpu": sm["r1"] - sm["r0"],
                      "spmv_per_rank_avg_launch_ms": [round(t, 5) for t in sp_ms], "spmv_layout_rank0": sm["layout"]}
     surface = None
-    if rank == 0 and world == 1 and args.surface_cycles > 0:
+    if args.full and rank == 0 and world == 1 and args.surface_cycles > 0:
         surface = surface_rate(mpg, A, b, xt, opts, args.surface_cycles, solve_rate)
     roofline = None
     cpu = None
-    if rank == 0:
+    if args.full and rank == 0:
         peak_read = mpg.bw_probe("read", 2 << 30, 3, local_rank)
         peak_copy = mpg.bw_probe("copy", 1 << 30, 3, local_rank)
         measured = max(peak_read, peak_copy)
@@ -823,7 +875,7 @@ def main():
         line = {
             "metric": METRIC, "value": round(value, 2), "unit": "GMRES iterations/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32",
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "full": args.full,
             "accum": {"f32": "f32: every dot / norm / gemv / SpMV partial sum of the fp32 Arnoldi in fp32 (the "
                              "reference's cblas_s* / mkl_sparse_s_mv class)",
                       "f64": "f64: the fp32 Arnoldi's products summed in fp64, rounded once"}[args.accum],
@@ -842,7 +894,7 @@ def main():
                                    f"{args.orth}, {args.prec} preconditioner, tol=0",
                        "step": f"one restart cycle = {args.rlen} iterations",
                        "value_counts": "GMRES iterations of the one (row-partitioned) solve per second",
-                       "rows_per_gpu": (r1 - r0), "nnz": global_nnz, "spmv_storage": sp["layout"],
+                       "rows_per_gpu": (r1 - r0), "nnz": global_nnz, "spmv_storage": layout,
                        "parallelism": (f"row-partition x{world} (halo send/recv + fp64 all-reduce over {transport})"
                                        if world > 1 else "one GPU")},
         }

@@ -185,3 +185,54 @@ def test_spmv_roofline_falls_back_on_a_degenerate_difference():
         assert sp["timing"] == "eager" and sp["avg_launch_ms"] == 0.0125
     sp = bench.spmv_roofline(_FakeEngine(0.011, 0.011), 3)
     assert sp["timing"] == "dup" and sp["avg_launch_ms"] == 0.011
+
+
+# ---- --dump-outputs: the timed solve's result as .npy files, bounded in size
+
+
+class _ReportEngine:
+    def __init__(self, n, steps):
+        self.n, self.steps = n, steps
+
+    def report(self, cycle_cap, step_cap):
+        import argparse
+
+        import numpy as np
+
+        assert cycle_cap >= self.steps and step_cap >= 30 * self.steps  # nothing of the run is cut off
+        cyc = np.arange(self.steps, dtype=np.float64)
+        return argparse.Namespace(x=np.arange(self.n, dtype=np.float64), cyc_r_norm=cyc, cyc_normalization=cyc + 1,
+                                  cyc_beta=cyc + 2, step_res=np.arange(30 * self.steps, dtype=np.float64),
+                                  res_norm=0.5, err_norm=0.25)
+
+
+def test_dump_outputs_writes_the_report(tmp_path):
+    import argparse
+
+    import numpy as np
+
+    args = argparse.Namespace(warmup=2, steps=3, rlen=30)
+    bench.dump_outputs(_ReportEngine(1000, 5), args, 1, 0, tmp_path / "d")
+    got = {f.stem: np.load(f) for f in (tmp_path / "d").iterdir()}
+    assert sorted(got) == ["cyc_beta", "cyc_normalization", "cyc_r_norm", "final_norms", "step_res", "x"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["x"], np.arange(1000.0)) and got["final_norms"].tolist() == [0.5, 0.25]
+    assert np.array_equal(got["step_res"], np.arange(150.0)) and np.array_equal(got["cyc_beta"], np.arange(5.0) + 2)
+    # a row-partitioned run: every rank its rows, the histories from rank 0 alone
+    bench.dump_outputs(_ReportEngine(10, 5), args, 2, 1, tmp_path / "r")
+    assert [f.name for f in (tmp_path / "r").iterdir()] == ["x_rank1.npy"]
+
+
+def test_dump_outputs_samples_a_long_x_the_same_way_every_time(tmp_path):
+    import argparse
+
+    import numpy as np
+
+    args = argparse.Namespace(warmup=2, steps=3, rlen=30)
+    n = bench.DUMP_X_ROWS + 12345
+    for d in ("a", "b"):
+        bench.dump_outputs(_ReportEngine(n, 5), args, 1, 0, tmp_path / d)
+    xa, xb = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert xa.size == bench.DUMP_X_ROWS and np.array_equal(xa, xb)
+    assert np.all(np.diff(xa) > 0) and xa[-1] < n  # distinct rows of x, ascending
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES

@@ -20,13 +20,17 @@
 set -u
 tag=${1:?usage: tools/battery.sh TAG step...}
 shift
-nob="--no-cpu-baseline --hbm-rows 0 --surface-cycles 0"
+# (bench.py measures the rooflines, the surface and the CPU baseline only with --full)
+nob="--full --no-cpu-baseline --hbm-rows 0 --surface-cycles 0"
+# the --full bench lines
+out=${MPG_OUT_DIR:-bench_out}
+mkdir -p "$out"
 cmds=()
 for s in "$@"; do
   case $s in
     suite) cmds+=("${tag}_suite|900|python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider") ;;
     smoke) cmds+=("${tag}_smoke|240|python -u -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")'") ;;
-    bench) cmds+=("${tag}_bench|420|python -u bench.py > gpurun_out/${tag}_bench.json") ;;
+    bench) cmds+=("${tag}_bench|420|python -u bench.py --full > $out/${tag}_bench.json") ;;
     bench100) cmds+=("${tag}_b100|240|python -u bench.py --rlen 100 --steps 5 --warmup 1 $nob > gpurun_out/${tag}_b100.json") ;;
     prof) cmds+=("${tag}_prof|300|rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_prof -o bench -- python3 bench.py --steps 10 $nob > gpurun_out/${tag}_prof_bench.json") ;;
     pmcf) cmds+=("${tag}_pmcf|150|timeout -s KILL 140 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/${tag}_pmc_fetch -o fetch -- python3 bench.py --steps 3 --warmup 1 $nob") ;;
@@ -51,7 +55,7 @@ for s in "$@"; do
     surfirr) for sp in fem27:111 stencil27:111; do
                cmds+=("${tag}_surf_${sp%%:*}|400|python -u tools/surface_vs_fused.py cgs --spec=$sp --cycles=10")
              done ;;
-    n2) cmds+=("${tag}_n2|400|MPG_BENCH_SHARED_GPU=1 python -u bench.py --gpus 2 --steps 5 --warmup 1 > gpurun_out/${tag}_bench_n2.json") ;;
+    n2) cmds+=("${tag}_n2|400|MPG_BENCH_SHARED_GPU=1 python -u bench.py --full --gpus 2 --steps 5 --warmup 1 > $out/${tag}_bench_n2.json") ;;
     *) echo "unknown step $s" >&2; exit 2 ;;
   esac
 done

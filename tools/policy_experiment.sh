@@ -6,11 +6,13 @@
 # usage (on the box): bash tools/policy_experiment.sh
 set -u
 mkdir -p gpurun_out
+out=${MPG_OUT_DIR:-bench_out}  # the bench lines (--full: the roofline is read below)
+mkdir -p "$out"
 bench() {  # name [env...]
   local name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --steps 20 --no-cpu-baseline > gpurun_out/pol_$name.json 2> gpurun_out/pol_$name.err
+  env "$@" timeout -k 10 300 python bench.py --full --steps 20 --no-cpu-baseline > $out/pol_$name.json 2> $out/pol_$name.err
   local rc=$?
-  echo "[$name] rc=$rc $(python -c "import json;d=json.loads(open('gpurun_out/pol_$name.json').read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d['roofline']['avg_launch_ms'])" 2>/dev/null)"
+  echo "[$name] rc=$rc $(python -c "import json;d=json.loads(open('$out/pol_$name.json').read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d['roofline']['avg_launch_ms'])" 2>/dev/null)"
   return $rc
 }
 run() {  # name flags
