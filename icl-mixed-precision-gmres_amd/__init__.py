@@ -204,6 +204,8 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_half_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.mpg_engine_slices_per_wave.argtypes = [C.c_void_p]
     lib.mpg_engine_givens_folded.argtypes = [C.c_void_p]
+    lib.mpg_engine_step_dots_steps.argtypes = [C.c_void_p]
+    lib.mpg_engine_step_dots_status.argtypes = [C.c_void_p, C.c_int]
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
     lib.mpg_engine_prologue_format.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.argtypes = [C.c_void_p]
@@ -897,16 +899,26 @@ class Engine:
 
     def spmv_layout(self) -> dict:
         """Storage of the Arnoldi SpMV: {"format": "csr"|"sell", "vec_width",
-        "col_bytes", "stored"} (mpg_engine_spmv_layout)."""
+        "col_bytes", "stored"} (mpg_engine_spmv_layout). An engine whose cycle
+        runs the SpMV inside the panel dots' launch (MPG_STEP_DOTS) also
+        reports "dots_fused": the number of such steps per cycle (the key is
+        absent when there are none)."""
         f, w, cb, st, win = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         if self._lib.mpg_engine_spmv_layout(self._h, C.byref(f), C.byref(w), C.byref(cb), C.byref(st), C.byref(win)):
             raise RuntimeError("mpg_engine_spmv_layout failed")
-        return {"format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
+        fused = int(self._lib.mpg_engine_step_dots_steps(self._h))
+        return {**({"dots_fused": fused} if fused > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
                 "stored": st.value, "window": bool(win.value),
                 "slices_per_wave": int(self._lib.mpg_engine_slices_per_wave(self._h)),
                 "givens_folded": bool(self._lib.mpg_engine_givens_folded(self._h) == 1),
                 "accum": {0: "f64", 1: "f32"}[int(self._lib.mpg_engine_accum(self._h))],
                 "prologue": {1: "csr", 2: "sell", 3: "node"}[int(self._lib.mpg_engine_prologue_format(self._h))]}
+
+    def step_dots_status(self, k: int) -> int:
+        """Status mpg_arnoldi_step_dots's support check gives at step k (0:
+        the SpMV can run inside the dots' launch; MPG_ERR_UNSUPPORTED, -5:
+        it cannot), without launching (mpg_engine_step_dots_status)."""
+        return int(self._lib.mpg_engine_step_dots_status(self._h, k))
 
     def sell_columns(self) -> dict:
         """Column form of the Arnoldi SpMV's SELL copy (mpg_engine_sell_columns):

@@ -1087,8 +1087,24 @@ __global__ __launch_bounds__(BS) void k_panel_dots(int n, const T* __restrict__ 
 // count the compiler guarded each column's load with its own branch and
 // waited for it before the next (one memory latency per column: t(k) =
 // 8.6 + 0.50 k us for the dots on BAND-10M, tools/per_step.py).
-template <class T, int BS, int NC, class A = double>
-__device__ __forceinline__ void dots_panel(int n, const T* __restrict__ V, int64_t ld, const T* __restrict__ w,
+// Where dots_panel_from reads w and the newest column V(:, NC - 1) from. DotsGlobal:
+// global memory (k_dots_nc, k_dots_panels). A staged source (k_step_dots,
+// DotsStaged) hands out the workgroup's own rows of both from LDS, where the
+// SpMV phase of the same launch left them, and may hold the lane's first
+// batch of earlier columns, loaded ahead of that phase (kHeld > 0: columns
+// 0..kHeld-1 of the lane's first row group, in held[]).
+template <class T, class A>
+struct DotsGlobal {
+    static constexpr bool kStaged = false;
+    static constexpr int kHeld = 0;
+    const T* __restrict__ w;
+    Raw4<T> held[1];
+    __device__ __forceinline__ void load_w(int i, A (&wv)[4]) const { Row4<T>::load(w + i, wv); }
+    __device__ __forceinline__ Raw4<T> newest(int) const { return Raw4<T>(); }
+};
+
+template <class T, int BS, int NC, class A = double, class SRC>
+__device__ __forceinline__ void dots_panel_from(int n, const T* __restrict__ V, int64_t ld, const SRC& src,
                                            double* __restrict__ partial) {
     static_assert(NC >= 1 && NC <= kNC, "one panel");
     constexpr int NP = Pow2Ceil<NC>::v;
@@ -1097,15 +1113,20 @@ __device__ __forceinline__ void dots_panel(int n, const T* __restrict__ V, int64
 #pragma unroll
     for (int c = 0; c < NP; ++c) acc[c] = A(0);
     const int n4 = n & ~3;
+    bool first = SRC::kHeld > 0;
     for (int i = 4 * (blockIdx.x * BS + threadIdx.x); i < n4; i += 4 * gridDim.x * BS) {
         A wv[4];
-        Row4<T>::load(w + i, wv);
+        src.load_w(i, wv);
 #pragma unroll
         for (int c0 = 0; c0 < NC; c0 += B) {
             Raw4<T> v[B];
 #pragma unroll
             for (int u = 0; u < B; ++u)
-                if (c0 + u < NC) v[u].load(V + (int64_t)(c0 + u) * ld + i);
+                if (c0 + u < NC) {
+                    if (SRC::kStaged && c0 + u == NC - 1) v[u] = src.newest(i);
+                    else if (c0 + u < SRC::kHeld && first) v[u] = src.held[c0 + u < SRC::kHeld ? c0 + u : 0];
+                    else v[u].load(V + (int64_t)(c0 + u) * ld + i);
+                }
             __builtin_amdgcn_sched_barrier(0);  // keep the batch's loads issued back to back
 #pragma unroll
             for (int u = 0; u < B; ++u)
@@ -1117,13 +1138,23 @@ __device__ __forceinline__ void dots_panel(int n, const T* __restrict__ V, int64
             // (128 VGPRs, 180 B of scratch per lane)
             asm volatile("" : "+v"(acc[c0]) : : "memory");
         }
+        if constexpr (SRC::kHeld > 0) first = false;
     }
-    for (int i = n4 + blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
-        const A wi = (A)w[i];
+    // tail rows (n not a multiple of 4; a staged source runs only where there are none)
+    if constexpr (!SRC::kStaged) {
+        for (int i = n4 + blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
+            const A wi = (A)src.w[i];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) acc[c] += (A)V[(int64_t)c * ld + i] * wi;
+            for (int c = 0; c < NC; ++c) acc[c] += (A)V[(int64_t)c * ld + i] * wi;
+        }
     }
     store_partials<NP, BS>(acc, NC, partial);
+}
+
+template <class T, int BS, int NC, class A = double>
+__device__ __forceinline__ void dots_panel(int n, const T* __restrict__ V, int64_t ld, const T* __restrict__ w,
+                                           double* __restrict__ partial) {
+    dots_panel_from<T, BS, NC, A>(n, V, ld, DotsGlobal<T, A>{w, {}}, partial);
 }
 
 template <class T, int BS, int NC, bool STAMP = false, class A = double>
@@ -1133,6 +1164,179 @@ __global__ __launch_bounds__(BS) void k_dots_nc(int n, const T* __restrict__ V, 
     stamp_at<STAMP>(stamp, 0);
     dots_panel<T, BS, NC, A>(n, V, ld, w, partial);
     stamp_at<STAMP>(stamp, 1);
+}
+
+// ---------------------------------------------------------------- step: SpMV + panel dots
+// The Arnoldi SpMV of step k inside the panel dots' launch (fp32 basis and
+// values, the uniform pair storage with the v_k window; one pass: n <= 4096
+// kCombineGroups, n % 4 == 0). The grid and the row ownership are k_dots_nc's:
+// workgroup b (1024 threads) owns rows [4096 b, 4096 b + 4096), lane t the row
+// group 4 (1024 b + t) -- 64 whole SELL-64 slices, four per wave. The
+// workgroup forms v_k = T(w_prev * inv) for its rows and 64 on either side in
+// one LDS window (every gather of its slices falls inside), runs
+// k_step_sell2's row sums on it, stores w and v_k, and leaves its rows of w in
+// LDS beside the window. dots_panel then runs on the staged w and v_k and the
+// global V(:, 0..k-1): the same products, the same order and the same Gd
+// partials per column as k_dots_nc after k_step_sell2, with no second launch
+// and no re-read of w and v_k. PF: the lane's first batch of earlier columns
+// is issued behind the slices' loads, so its latency runs under the row sums.
+// FOLD as in k_step_sell2: every workgroup sums the <= kBlock ||w||^2
+// partials in waves 0..3 in the same fixed order (the other waves hold none).
+constexpr int kStepDotsRows = 4 * kCombineBlock;  // rows of a workgroup
+
+template <class T, class A, int HELD>
+struct DotsStaged {
+    static constexpr bool kStaged = true;
+    static constexpr int kHeld = HELD;
+    const T* wst;   // LDS: w of this workgroup's rows
+    const T* vkst;  // LDS: v_k of this workgroup's rows
+    int base;       // its first row
+    Raw4<T> held[HELD > 0 ? HELD : 1];
+    __device__ __forceinline__ void load_w(int i, A (&wv)[4]) const { Row4<T>::load(wst + (i - base), wv); }
+    __device__ __forceinline__ Raw4<T> newest(int i) const {
+        Raw4<T> r;
+        r.load(vkst + (i - base));
+        return r;
+    }
+};
+
+template <class T, class P, int W, bool FOLD, int BE, int NC, bool PF, class A>
+__global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices, const int16_t* __restrict__ col,
+                                                             const T* __restrict__ val, const T* __restrict__ wprev,
+                                                             const T* __restrict__ inv_p, T* __restrict__ V,
+                                                             int64_t ld, int k, const P* __restrict__ diag,
+                                                             T* __restrict__ w, GivensFold<T> fold,
+                                                             const int32_t* __restrict__ spat,
+                                                             const int64_t* __restrict__ coff,
+                                                             const int16_t* __restrict__ pat, int64_t ustride,
+                                                             double* __restrict__ dpart) {
+    static_assert(std::is_same_v<T, float>, "fp32 basis and values");
+    using CI = int16_t;
+    using Row = SellRow<T, CI, W, (MPG_SELL_NT != 0), BE>;
+    constexpr int BS = kCombineBlock, SPW = 4;
+    constexpr int RB = kStepDotsRows, WL = kWinLo + RB + kWinHi;  // the workgroup's window of v_k
+    static_assert(SPW * (BS / kWave) * kWave == RB, "four slices per wave cover the workgroup's rows");
+    __shared__ __attribute__((aligned(16))) T win[WL];
+    __shared__ __attribute__((aligned(16))) T wst[RB];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = wave_id();
+    const int base = (int)blockIdx.x * RB;
+    const int s0 = (int)blockIdx.x * (RB / kWave) + wid * SPW;
+    // 0. the slices' offsets (computed) and pattern indices
+    Row row[SPW];
+    bool live_p[SPW];
+#pragma unroll
+    for (int p = 0; p < SPW; ++p) {
+        live_p[p] = s0 + p < nslices;  // a dead wave still joins every barrier
+        row[p].init_uniform(live_p[p] ? s0 + p : 0, ustride, spat, coff);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // 1. the fold's ||w||^2 partial: one per lane of the first kBlock lanes
+    A part = A(0);
+    if constexpr (FOLD) {
+        part = (A)fold.norm2[tid < fold.nparts ? tid : 0];
+        if (tid >= fold.nparts) part = A(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // 2. the window of w_prev, raw: the lane's own row group and, in the
+    // first 128 lanes, one entry of the 64 rows on either side (clamped
+    // addresses; n % 4 == 0, so a row group lies inside [0, n) or outside)
+    const int i4 = base + 4 * tid;
+    const bool in4 = i4 < n;
+    Raw4<T> wr;
+    wr.load(wprev + (in4 ? i4 : 0));
+    const int hc = tid < kWinLo ? base - kWinLo + tid : base + RB + (tid - kWinLo);
+    const bool hin = tid < kWinLo + kWinHi && hc >= 0 && hc < n;
+    const T wh = wprev[hin ? hc : 0];
+    __builtin_amdgcn_sched_barrier(0);
+    // 3. the slices' first batches: values first, then the columns
+#pragma unroll
+    for (int p = 0; p < SPW; ++p) {
+        row[p].init_vals(lane, val);
+        row[p].load_vals(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < SPW; ++p) {
+        row[p].init_finish(lane, col, val, nullptr, pat);
+        row[p].load_cols(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // 4. PF: the dots' first batch of earlier columns at the lane's row group
+    constexpr int B = kColBatch<T>;
+    // (with the fold 6 columns: 8 held across the partial sums spilled, 20-28 B per lane)
+    constexpr int HMAX = FOLD ? 6 : B;
+    constexpr int HELD = !PF ? 0 : NC - 1 < HMAX ? NC - 1 : HMAX;
+    DotsStaged<T, A, HELD> src;
+    src.wst = wst;
+    src.vkst = win + kWinLo;
+    src.base = base;
+    if constexpr (HELD > 0) {
+#pragma unroll
+        for (int u = 0; u < HELD; ++u) src.held[u].load(V + (int64_t)u * ld + (in4 ? i4 : 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    T inv;
+    double nrm2sq = 0.0;
+    if constexpr (FOLD) {
+        constexpr int NG = kBlock / kWave;  // the waves that hold partials
+        __shared__ A scratch[NG];
+        __shared__ T inv_s;
+        if (fold.nparts > 0) {
+            if (wid < NG) {
+                const A v = wave_sum(part + A(0));
+                if (lane == 0) scratch[wid] = v;
+            }
+            lds_barrier();
+            A r = A(0);
+#pragma unroll
+            for (int q = 0; q < NG; ++q) r += scratch[q];
+            nrm2sq = (double)r;
+        } else {
+            nrm2sq = fold.norm2[0];
+        }
+        if (tid == 0) inv_s = inv_of_norm2<T>(nrm2sq);
+        lds_barrier();
+        inv = inv_s;
+    } else {
+        inv = *inv_p;
+    }
+    // the window of v_k = T(w_prev * inv), zero outside [0, n)
+    {
+        T vq[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) vq[r] = in4 ? (T)(wr.template at<T>(r) * inv) : T(0);
+        Row4<T>::store(win + kWinLo + 4 * tid, vq);
+        if (tid < kWinLo + kWinHi) win[tid < kWinLo ? tid : RB + tid] = hin ? (T)(wh * inv) : T(0);
+    }
+    lds_barrier();
+    auto xv = [&](int c) { return (double)win[c - base + kWinLo]; };
+    A sum[SPW] = {};
+#pragma unroll
+    for (int p = 0; p < SPW; ++p)
+        if (live_p[p]) row[p].sum(0, xv, sum[p]);
+#pragma unroll
+    for (int p = 0; p < SPW; ++p) {
+        if (live_p[p])
+            for (int q = Row::U; q < row[p].steps; q += Row::U) {
+                row[p].load(q);
+                row[p].sum(q, xv, sum[p]);
+            }
+        const int i = (s0 + p) * kWave + lane;
+        T wi = T(0);
+        if (live_p[p] && i < n) {
+            const T t = (T)sum[p];  // spmv(1, A, v, 0, w): y = 1*t
+            wi = precond<T, P>(t, diag, i);
+            w[i] = wi;
+            V[(int64_t)k * ld + i] = win[i - base + kWinLo];
+        }
+        wst[i - base] = wi;  // rows past n: an exact 0, and no row group of theirs is read
+    }
+    lds_barrier();
+    dots_panel_from<T, BS, NC, A>(n, V, ld, src, dpart);
+    if constexpr (FOLD) {
+        __shared__ T col_s[kFoldMaxM + 2], c_s[kFoldMaxM + 2], s_s[kFoldMaxM + 2];
+        if (blockIdx.x == 0) givens_block(fold.g, nrm2sq, col_s, c_s, s_s);
+    }
 }
 
 // V^T w for nc > kNC columns in ONE launch (GMRES(100): the round-3 form ran
@@ -1841,6 +2045,11 @@ struct mpg_arnoldi {
     double* fd_part = nullptr;
     unsigned* fd_cnt = nullptr;
     int fd_gs = 0, fd_ng = 0;
+    // the SpMV in the dots' launch (k_step_dots): the ||w||^2 partials step
+    // sd_k's launch folded, so that a repeat of that launch right behind it
+    // (the duplicate of a measurement) folds the same ones, not its own dots'
+    int sd_k = -1, sd_G = 0;
+    double* sd_part = nullptr;
     // fp32 Arnoldi with fp32 accumulation (mpg_arnoldi_set_accum): the
     // launches go through arnoldi_acc32.hip's A = float instantiations
     bool acc32 = false;

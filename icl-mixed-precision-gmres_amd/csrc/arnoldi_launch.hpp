@@ -194,6 +194,73 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
 }
 
 
+// The SpMV of step k inside the panel dots' launch (k_step_dots): MPG_OK when
+// this workspace, accumulation class and step can run it, MPG_ERR_UNSUPPORTED
+// otherwise (the caller then launches the SpMV and the dots apart). Built for
+// the fp32 accumulation class on BAND's storage: uniform int16 slices of at
+// most 10 entries per row in 2-wide steps, the v_k window, fp32 basis and values.
+// (The fp64 class is not built: the held batch beside four slices' first
+// batches and 32 fp64 accumulators does not fit 128 VGPRs.)
+template <class A>
+int step_dots_check(const mpg_arnoldi* a, int k) {
+    if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
+    const SellCopy& S = a->sell;
+    const bool ok = std::is_same_v<A, float> && (a->combo == 2 || a->combo == 3) &&  // fp32 basis, fp32 values
+                    a->d.orth != kOrthMGS && a->d.orth != kOrthCGSR && k + 1 <= kNC &&
+                    a->d.n > 0 && a->d.n % 4 == 0 &&  // (dots_panel's tail rows belong to workgroup 0's sums)
+                    (int64_t)a->Gd * kStepDotsRows >= a->d.n &&  // one pass
+                    a->front == 0 && a->d.n_ext == a->d.n &&     // one GPU: no halo rows
+                    // (k_step_sell2's storage; a copy of one slice, which the pair kernel leaves
+                    // to k_step_sell, runs here too: the row sums are the same in every form)
+                    S.nslices > 0 && S.c16 && S.win && !S.rows && sell_uniform(S) && S.W == 2 &&
+                    S.ustride / kWave <= 10;
+    return ok ? MPG_OK : MPG_ERR_UNSUPPORTED;
+}
+
+template <class A>
+int step_dots_run(mpg_arnoldi_t a, int k, int fold) {
+    if (!a || k < 0 || k >= a->d.m || fold < 0 || fold > 2) return MPG_ERR_ARG;
+    if (int st = step_dots_check<A>(a, k)) return st;
+    if (fold && (k < 1 || a->d.m > kFoldMaxM)) return MPG_ERR_ARG;
+    if constexpr (std::is_same_v<A, float>) {
+        using T = float;
+        using P = float;
+        // a repeat of step k's launch right behind it folds what the first folded
+        const bool again = fold == 2 && a->sd_k == k && a->last_part == a->dpart;
+        if (fold == 2 && !again) {
+            a->sd_k = k;
+            a->sd_part = a->last_part;
+            a->sd_G = a->last_G;
+        }
+        if (fold == 2 && (a->sd_G > kBlock || a->sd_part == a->dpart)) return MPG_ERR_ARG;  // <= kBlock partials, not its own output
+        GivensFold<T> gf{nullptr, 0, {}};
+        if (fold) gf = GivensFold<T>{fold == 2 ? a->sd_part : a->sums, fold == 2 ? a->sd_G : 0, givens_args<T>(a, k - 1)};
+        const SellCopy& S = a->sell;
+        const P* diag = a->d.jacobi ? static_cast<const P*>(a->d.diag) : nullptr;
+        int st = with_nc<kNC>(k + 1, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value;
+            auto go = [&](auto kern) {
+                launch_timed(a->ctx, kern, dim3(a->Gd), dim3(kCombineBlock), a->d.n, S.nslices,
+                             static_cast<const int16_t*>(S.col), static_cast<const T*>(S.val),
+                             static_cast<const T*>(a->w[k & 1]), static_cast<const T*>(a->inv()),
+                             static_cast<T*>(a->V), a->ld, k, diag, static_cast<T*>(a->w[(k + 1) & 1]), gf, S.spat,
+                             S.coff, static_cast<const int16_t*>(S.pat), S.ustride, a->dpart);
+                return (int)MPG_OK;
+            };
+            // (PF, the held first batch of basis columns: 27.54k against 27.05k it/s
+            // without it on BAND-10M, 3 interleaved runs each; only that form is built)
+            return fold ? go(k_step_dots<T, P, 2, true, 10, NC, true, A>) : go(k_step_dots<T, P, 2, false, 10, NC, true, A>);
+        });
+        if (st) return st;
+        a->last_G = a->Gd;
+        a->last_part = a->dpart;
+        MPG_LAUNCH_CHECK(a->ctx);
+        return MPG_OK;
+    } else {
+        return MPG_ERR_UNSUPPORTED;
+    }
+}
+
 // row groups per panel of k_dots_panels: about one workgroup per CU in all
 // (the same on every rank: uniform groups set Gd = kCombineGroups), so each
 // column has <= kCombineGroups / 2 partials for k_cgs_update_wide
@@ -466,6 +533,8 @@ int update_run(mpg_arnoldi_t a, int k) {
 namespace mpg_acc32 {
 int reduce(mpg_arnoldi* a, int ncols);
 int spmv(mpg_arnoldi* a, int k, int fold, bool dots);
+int step_dots(mpg_arnoldi* a, int k, int fold);
+int step_dots_ok(const mpg_arnoldi* a, int k);
 int dots(mpg_arnoldi* a, int k, bool combine);
 int cgs(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool no_next);
 int mgs(mpg_arnoldi* a, int k, int j, bool from_partials);

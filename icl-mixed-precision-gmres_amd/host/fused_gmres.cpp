@@ -84,6 +84,13 @@ public:
     bool needs_arnoldi_residual() const override { return true; }
 };
 
+// the unset MPG_STEP_DOTS policy: the steps (k + 1 in [lo, hi]) that take the
+// SpMV inside the dots' launch; lo > hi: none. BAND-10M, kernel trace of the
+// bench (profiles/r07_step_dots/): the one launch took less than k_step_sell2
+// + k_dots_nc at every k (12.5 against 14.6 us at k = 0, 29.7 against 30.4 at
+// k = 29) and saves the launch boundary between them, so every step takes it
+constexpr int kStepDotsLo = 1, kStepDotsHi = 32;
+
 }  // namespace
 
 struct FusedEngine::Impl {
@@ -120,6 +127,29 @@ struct FusedEngine::Impl {
     bool fuse_dots = false;     // ... from dots formed in the SpMV launch
     bool fuse_dots_required = false;
     int fuse_dots_k0 = 32;      // ... for the steps with k + 1 <= fuse_dots_k0
+    // the SpMV inside the dots' launch (mpg_arnoldi_step_dots; MPG_STEP_DOTS):
+    // 0 never, 1 wherever supported, 2 required, -1 the measured policy --
+    // the steps with step_dots_lo <= k + 1 <= step_dots_hi
+    int step_dots = 0;
+    int step_dots_lo = 1, step_dots_hi = 0;
+    int64_t dup_with_step = 0;  // time_phase_dup: CGS duplicates that re-ran that launch ahead of them
+    bool dup_step_only = false;  // ... duplicate that launch alone among the SpMV sites
+
+    // step k runs the SpMV and the dots in one launch
+    // (one GPU, plain CGS whose update sums the dots' partials itself, no ILU between the launches)
+    bool step_dots_engine_ok() const { return !(comm || ilu || orth != MPG_ORTH_CGS || !cgs_partials || combine); }
+    bool step_dots_at(int k) const {
+        if (step_dots == 0) return false;
+        if (step_dots == 2) return true;  // (an unsupported step is then an error at its launch)
+        if (!step_dots_engine_ok()) return false;
+        if (step_dots < 0 && (k + 1 < step_dots_lo || k + 1 > step_dots_hi)) return false;
+        return mpg_arnoldi_step_dots_supported(arn, k) == MPG_OK;
+    }
+    int step_dots_steps() const {
+        int c = 0;
+        for (int k = 0; k < m; ++k) c += step_dots_at(k) && mpg_arnoldi_step_dots_supported(arn, k) == MPG_OK;
+        return c;
+    }
     int timed = -1;                  // phase whose launches time_phase brackets with events
     bool timed_inplace = false;      // ... the cycle's own SpMV launch, by its kernel events
     bool timed_graph = false;        // ... external event nodes around it in a captured cycle
@@ -418,6 +448,20 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     // steps, whose per-row basis loads are few; VERDICT r3 item 5's policy)
     const char* kenv = std::getenv("MPG_FUSE_DOTS_K0");
     I.fuse_dots_k0 = kenv && *kenv ? std::max(0, std::min(32, std::atoi(kenv))) : 32;
+    // MPG_STEP_DOTS: the SpMV inside the panel dots' launch (k_step_dots).
+    // 0 never, 1 wherever the launch is supported, 2 required (an unsupported
+    // step is an error; tests); unset: the steps with kStepDotsLo <= k + 1 <=
+    // kStepDotsHi, where the one launch measured faster than the two on
+    // BAND-10M in the fp32 accumulation class, the only one it is built for
+    // (profiles/r07_step_dots/). MPG_STEP_DOTS_LO / _HI move the range.
+    {
+        const char* senv = std::getenv("MPG_STEP_DOTS");
+        I.step_dots = senv && *senv >= '0' && *senv <= '2' ? *senv - '0' : -1;
+        const char* lo = std::getenv("MPG_STEP_DOTS_LO");
+        const char* hi = std::getenv("MPG_STEP_DOTS_HI");
+        I.step_dots_lo = lo && *lo ? std::atoi(lo) : kStepDotsLo;
+        I.step_dots_hi = hi && *hi ? std::atoi(hi) : kStepDotsHi;
+    }
     // MPG_FOLD_GIVENS: 0 never, 1 always (m permitting), unset: where it pays
     // (mpg_arnoldi_fold_pays: up to ~4k SpMV workgroups)
     const char* fenv = std::getenv("MPG_FOLD_GIVENS");
@@ -511,6 +555,43 @@ void FusedEngine::step(int k, bool fold) {
         }
         if (st != MPG_ERR_UNSUPPORTED || I.fuse_dots_required) check(st, "spmv+dots", I.ctx);
         I.fuse_dots = false;  // not available for this storage: the separate launches below
+    }
+    // the SpMV inside the panel dots' launch, then straight to the update
+    // that sums the dots' partials itself (MPG_STEP_DOTS; same bits)
+    if (I.step_dots_at(k)) {
+        const int f = fold && k > 0 ? 2 : 0;
+        if (!I.step_dots_engine_ok())
+            throw StatusError(MPG_ERR_UNSUPPORTED, "MPG_STEP_DOTS=2: the SpMV + dots launch needs one GPU and plain CGS "
+                                                   "with in-launch sums, without ILU");
+        timed(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
+        const int st = mpg_arnoldi_step_dots(I.arn, k, f);
+        if (st == MPG_OK) {
+            dup(0, [&] { check(mpg_arnoldi_step_dots(I.arn, k, f), "spmv+dots", I.ctx); });
+            timed_end(0);
+            timed(2, [&] { check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx); });
+            check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx);
+            // (the update's own partials replaced nothing the launch before it
+            // reads, but its duplicate needs w = A v_k and the dots again: the
+            // one launch is re-run ahead, and time_phase_dup takes its share out)
+            dup(2, [&] {
+                check(mpg_arnoldi_step_dots(I.arn, k, f), "spmv+dots", I.ctx);
+                check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx);
+                ++I.dup_with_step;
+            });
+            timed_end(2);
+            if (!fold) givens(k);
+            return;
+        }
+        timed_end(0);
+        check(st, "spmv+dots", I.ctx);  // (step_dots_at asked: unsupported here means MPG_STEP_DOTS=2)
+    }
+    if (I.dup_step_only && I.dup_phase == 0) {
+        // (time_phase_dup's own correction run: only the launches above are doubled)
+        const int keep = I.dup_phase;
+        I.dup_phase = -1;
+        step(k, fold);
+        I.dup_phase = keep;
+        return;
     }
     if (fold && k > 0) {
         if (I.comm)  // the ||w||^2 partials' all-reduce and the w_prev halo in one RCCL group
@@ -963,15 +1044,25 @@ double FusedEngine::phase_bytes(int which) const {
         int32_t fmt = 0, W = 0, cb = 0, win = 0;
         int64_t stored = 0;
         check(mpg_arnoldi_spmv_layout(I.arn, &fmt, &W, &cb, &stored, &win), "layout", I.ctx);
-        const double vec = 3 * n * sT + jac * n * sP;
+        // (steps that run the SpMV inside the dots' launch also read
+        // V(:,0..k-1) there: their columns, averaged over the cycle's steps)
+        double cols = 0;
+        for (int k = 0; k < I.m; ++k)
+            if (I.step_dots_at(k)) cols += k;
+        const double vec = 3 * n * sT + jac * n * sP + cols / I.m * n * sT;
         if (fmt == 2 || fmt == 3) return (double)mpg_arnoldi_sell_matrix_bytes(I.arn) + vec;  // (3: node blocks)
         return z * (sV + 4) + (n + 1) * 4 + vec;
     }
     if (which == 3) {
-        // panel dots, mean over k: V(:,0..k) and w read
-        double cols = 0;
-        for (int k = 0; k < I.m; ++k) cols += (I.orth == MPG_ORTH_MGS ? 1 : k + 1);
-        return (cols / I.m + 1) * n * sT;
+        // panel dots, mean over k: V(:,0..k) and w read (per step of the
+        // cycle: a step whose dots ride in the SpMV's launch adds nothing here)
+        double cols = 0, launches = 0;
+        for (int k = 0; k < I.m; ++k)
+            if (!I.step_dots_at(k)) {
+                cols += (I.orth == MPG_ORTH_MGS ? 1 : k + 1);
+                launches += 1;
+            }
+        return (cols / I.m + launches / I.m) * n * sT;
     }
     // CGS update at mean k: read V(:,0..k), read + write w
     return ((I.m - 1) / 2.0 + 1) * n * sT + 2 * n * sT;
@@ -980,6 +1071,8 @@ double FusedEngine::phase_bytes(int which) const {
 mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
 bool FusedEngine::givens_folded() const { return p_->fold; }
+int FusedEngine::step_dots_steps() const { return p_->step_dots_steps(); }
+int FusedEngine::step_dots_status(int k) const { return mpg_arnoldi_step_dots_supported(p_->arn, k); }
 
 // Device-event time of one phase kernel in its place in the cycle: `reps`
 // restart cycles run eagerly in cycle order, and at every launch of phase
@@ -1253,6 +1346,7 @@ double FusedEngine::time_phase_dup(int which, int reps, int64_t* launches) {
     hipEvent_t ev[2] = {nullptr, nullptr};
     auto cleanup = [&] {
         I.dup_phase = -1;
+        I.dup_step_only = false;
         for (int q = 0; q < 2; ++q) {
             if (ge[q]) (void)hipGraphExecDestroy(ge[q]);
             if (g[q]) (void)hipGraphDestroy(g[q]);
@@ -1260,12 +1354,17 @@ double FusedEngine::time_phase_dup(int which, int reps, int64_t* launches) {
         }
     };
     std::vector<double> diff;
-    int64_t added = 0, with_dots = 0;
+    int64_t added = 0, with_dots = 0, with_step = 0;
+    // (set by the correction run below for its own call only)
+    const bool step_only = I.dup_step_only;
+    I.dup_step_only = false;
     try {
         for (int q = 0; q < 2; ++q) {
             I.dup_phase = q ? which : -1;
+            I.dup_step_only = q && step_only;
             I.dup_count = 0;
             I.dup_with_dots = 0;
+            I.dup_with_step = 0;
             hipck(hipStreamBeginCapture(I.stream(), hipStreamCaptureModeThreadLocal), "begin capture");
             try {
                 cycle_program();
@@ -1278,9 +1377,11 @@ double FusedEngine::time_phase_dup(int which, int reps, int64_t* launches) {
             if (q) {
                 added = I.dup_count;
                 with_dots = I.dup_with_dots;
+                with_step = I.dup_with_step;
             }
         }
         I.dup_phase = -1;
+        I.dup_step_only = false;
         if (added < 1) throw StatusError(MPG_ERR_UNSUPPORTED, "the cycle has no launch of that phase");
         for (hipEvent_t& e : ev) hipck(hipEventCreate(&e), "event");
         for (int q = 0; q < 2; ++q) hipck(hipGraphLaunch(ge[q], I.stream()), "graph launch");  // warm
@@ -1306,6 +1407,10 @@ double FusedEngine::time_phase_dup(int which, int reps, int64_t* launches) {
     std::sort(diff.begin(), diff.end());
     double ms = diff[diff.size() / 2];
     if (with_dots) ms -= time_phase_dup(3, reps) * (double)with_dots / (double)added;
+    if (with_step) {  // updates behind the SpMV + dots launch: that launch's share, measured on those steps alone
+        I.dup_step_only = true;
+        ms -= time_phase_dup(0, reps) * (double)with_step / (double)added;
+    }
     return ms;
 }
 
@@ -1530,6 +1635,16 @@ int mpg_engine_prologue_format(mpg_engine_t e) {
 int mpg_engine_givens_folded(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return e->eng->givens_folded() ? 1 : 0;
+}
+
+int mpg_engine_step_dots_steps(mpg_engine_t e) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return e->eng->step_dots_steps();
+}
+
+int mpg_engine_step_dots_status(mpg_engine_t e, int k) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return e->eng->step_dots_status(k);
 }
 
 int mpg_engine_comm_ranks(mpg_engine_t e) {

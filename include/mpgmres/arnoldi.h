@@ -163,6 +163,17 @@ int mpg_arnoldi_givens_partials_spmv(mpg_arnoldi_t a, int k);
  * k + 1 <= 32). MPG_ERR_UNSUPPORTED unless the SpMV runs on the SELL copy
  * with an fp32 basis, fp32 values, 16-bit columns and the v_k window. */
 int mpg_arnoldi_spmv_dots(mpg_arnoldi_t a, int k, int fold);
+/* SpMV step k inside the panel dots' launch (fold as above): the dots' grid
+ * of 1024-lane workgroups, each forming its own 4096 rows of w and v_k, then
+ * the panel dots on them from LDS -- replaces spmv + dots ahead of
+ * mpg_arnoldi_cgs_partials with the same bits and the same partials (one GPU,
+ * plain CGS, k + 1 <= 32). MPG_ERR_UNSUPPORTED unless: fp32 accumulation
+ * (mpg_arnoldi_set_accum), fp32 basis and values, the uniform SELL copy of
+ * int16 column pairs with 10 entries per row and the v_k window, no halo
+ * rows, n % 4 == 0 and n <= 1,048,576 (one pass). _supported returns the
+ * status the launch would, without launching. */
+int mpg_arnoldi_step_dots(mpg_arnoldi_t a, int k, int fold);
+int mpg_arnoldi_step_dots_supported(mpg_arnoldi_t a, int k);
 int mpg_arnoldi_fold_max_m(void);
 /* 1 when folding the Givens step into the SpMV pays at this size (the SpMV's
  * workgroups each sum the partials; past ~4k workgroups a separate Givens

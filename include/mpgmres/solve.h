@@ -178,6 +178,11 @@ int64_t mpg_engine_sell_shared_slices(mpg_engine_t e);
 int mpg_engine_sell_sigma(mpg_engine_t e);
 /* 1: the Givens step of step k-1 rides SpMV(k) (mpg_arnoldi_fold_pays); 0: its own launch */
 int mpg_engine_givens_folded(mpg_engine_t e);
+/* steps of a restart cycle that run the SpMV inside the panel dots' launch
+ * (mpg_arnoldi_step_dots; MPG_STEP_DOTS), and the status that launch's
+ * support check gives at step k (MPG_OK / MPG_ERR_UNSUPPORTED) */
+int mpg_engine_step_dots_steps(mpg_engine_t e);
+int mpg_engine_step_dots_status(mpg_engine_t e, int k);
 /* the accumulation class the engine's Arnoldi runs: MPG_ACCUM_F64 0 / MPG_ACCUM_F32 1 (arnoldi.h) */
 int mpg_engine_accum(mpg_engine_t e);
 /* the residual prologue's storage (mpg_arnoldi_prologue_format: 1 CSR, 2 SELL, 3 node blocks) */
