@@ -207,6 +207,7 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_step_dots_steps.argtypes = [C.c_void_p]
     lib.mpg_engine_step_dots_status.argtypes = [C.c_void_p, C.c_int]
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
+    lib.mpg_engine_prec_fused.argtypes = [C.c_void_p]
     lib.mpg_engine_prologue_format.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.restype = C.c_int64
@@ -280,6 +281,11 @@ _HIP_DECLS.update({
     "mpg_copy_f32f64": ([_P, _I64, _P, _P], C.c_int),
     "mpg_copy_f64f16": ([_P, _I64, _P, _P], C.c_int),
     "mpg_copy_f32f16": ([_P, _I64, _P, _P], C.c_int),
+    "mpg_bjacobi_setup_f64": ([_P, _P, _P, _I32, _P, C.POINTER(_I32)], C.c_int),
+    "mpg_bjacobi_setup_f32": ([_P, _P, _P, _I32, _P, C.POINTER(_I32)], C.c_int),
+    "mpg_bjacobi_apply_f64": ([_P, _I64, _I32, _P, _P], C.c_int),
+    "mpg_bjacobi_apply_f32": ([_P, _I64, _I32, _P, _P], C.c_int),
+    "mpg_bjacobi_apply_f64_p32": ([_P, _I64, _I32, _P, _P], C.c_int),
     "mpg_nrm2_pair_host": ([_P, _I64, C.c_int, _P, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)],
                            C.c_int),
 })
@@ -499,11 +505,12 @@ class Result:
 def make_args(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, mode="mixed", orth="mgs",
               prec="identity", rlen=30, tol=1e-6, max_restarts=1_000_000, rtol=0.0, repeat_iter=False,
               orthloss=False, jacobi_steps=1, engine="fused", verbose=False, device=0, threads=0,
-              spmv_format="auto", half_unscaled=False, stop_on_breakdown=False, accum="f64"):
+              spmv_format="auto", half_unscaled=False, stop_on_breakdown=False, accum="f64", prec_block=3):
     """Build mpg_solve_args (shared by mpg_solve and the CPU oracle).
     accum: the fp32 Arnoldi's accumulation class, "f64" (fp32 products
     summed in fp64, rounded once) or "f32" (every partial sum in fp32: the
-    reference's cblas_s* / mkl_sparse_s_mv class; fused engine only)."""
+    reference's cblas_s* / mkl_sparse_s_mv class; fused engine only).
+    prec_block: unknowns per node of prec="bjacobi" (2, 3 or 4)."""
     b = np.ascontiguousarray(b, dtype=np.float64)
     keep = [A.rowptr, A.col, A.val, b]
     a = SolveArgs()
@@ -524,6 +531,7 @@ def make_args(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, mod
     a.half_unscaled = int(half_unscaled)
     a.stop_on_breakdown = int(stop_on_breakdown)
     a.accum = ACCUMS[accum]
+    a.prec_block = prec_block
     return a, keep
 
 
@@ -902,16 +910,20 @@ class Engine:
         "col_bytes", "stored"} (mpg_engine_spmv_layout). An engine whose cycle
         runs the SpMV inside the panel dots' launch (MPG_STEP_DOTS) also
         reports "dots_fused": the number of such steps per cycle (the key is
-        absent when there are none)."""
+        absent when there are none). With prec="bjacobi" it reports
+        "prec_fused": 1 when the block apply runs inside the SpMV launches, 0
+        when it is a launch of its own (mpg_engine_prec_fused)."""
         f, w, cb, st, win = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         if self._lib.mpg_engine_spmv_layout(self._h, C.byref(f), C.byref(w), C.byref(cb), C.byref(st), C.byref(win)):
             raise RuntimeError("mpg_engine_spmv_layout failed")
         fused = int(self._lib.mpg_engine_step_dots_steps(self._h))
+        pf = int(self._lib.mpg_engine_prec_fused(self._h))
         return {**({"dots_fused": fused} if fused > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
                 "stored": st.value, "window": bool(win.value),
                 "slices_per_wave": int(self._lib.mpg_engine_slices_per_wave(self._h)),
                 "givens_folded": bool(self._lib.mpg_engine_givens_folded(self._h) == 1),
                 "accum": {0: "f64", 1: "f32"}[int(self._lib.mpg_engine_accum(self._h))],
+                **({"prec_fused": pf} if pf >= 0 else {}),
                 "prologue": {1: "csr", 2: "sell", 3: "node"}[int(self._lib.mpg_engine_prologue_format(self._h))]}
 
     def step_dots_status(self, k: int) -> int:

@@ -135,6 +135,7 @@ int mpg_arnoldi_create(mpg_ctx_t ctx, const mpg_arnoldi_desc* desc, mpg_arnoldi_
     if (combo < 0) return MPG_ERR_UNSUPPORTED;
     if (desc->A->rows != desc->n || desc->A->cols > desc->n_ext) return MPG_ERR_ARG;
     if (desc->inner_row_exp && desc->inner_val != MPG_F16) return MPG_ERR_ARG;  // only fp16 copies are scaled
+    if (desc->block_dinv && (desc->jacobi || desc->prec_block < 2 || desc->prec_block > 4)) return MPG_ERR_ARG;
     mpg_arnoldi* a = new (std::nothrow) mpg_arnoldi();
     if (!a) return MPG_ERR_ALLOC;
     a->ctx = ctx;
@@ -263,9 +264,14 @@ int mpg_arnoldi_prologue(mpg_arnoldi_t a) {
                 N.tiles, N.bptr, static_cast<const char*>(N.recs), N.ntiles, N.nblk, tpw, node_xcd(N),
                 static_cast<const X*>(a->d.x), a->rsum);
             a->last_G = rb_grid(a);
-            k_prologue_rows<T, X, P><<<rb_grid(a), kBlock, 0, a->ctx->stream>>>(
-                A->blocks, A->nblocks, a->rsum, static_cast<const X*>(a->d.x), static_cast<const X*>(a->d.b), diag,
-                static_cast<T*>(a->w[0]), a->partial);
+            if (bj_fused(a))  // w = Dinv T(r) in the launch (the caller re-forms ||w||^2: mpg_arnoldi_prologue_wnorm)
+                k_prologue_rows<T, X, P, true><<<rb_grid(a), kBlock, 0, a->ctx->stream>>>(
+                    A->blocks, A->nblocks, a->rsum, static_cast<const X*>(a->d.x), static_cast<const X*>(a->d.b),
+                    static_cast<const P*>(a->d.block_dinv), static_cast<T*>(a->w[0]), a->partial);
+            else
+                k_prologue_rows<T, X, P><<<rb_grid(a), kBlock, 0, a->ctx->stream>>>(
+                    A->blocks, A->nblocks, a->rsum, static_cast<const X*>(a->d.x), static_cast<const X*>(a->d.b),
+                    diag, static_cast<T*>(a->w[0]), a->partial);
             return (int)MPG_OK;
         }
         const SellCopy* S = a->outer_is_inner ? &a->sell : &a->sell_outer;
@@ -302,6 +308,11 @@ int mpg_arnoldi_prologue(mpg_arnoldi_t a) {
     if (st) return st;
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
+}
+
+int mpg_arnoldi_prec_fused(mpg_arnoldi_t a, int which) {
+    if (!a || !bj_fused(a)) return 0;
+    return which == 0 ? 1 : which == 1 ? (a->node_res && a->rsum ? 1 : 0) : 0;
 }
 
 int mpg_arnoldi_prologue_wnorm(mpg_arnoldi_t a) {

@@ -162,7 +162,12 @@ __global__ __launch_bounds__(kBlock) void k_node_rowsums(const int32_t* __restri
         prod);
 }
 
-template <class T, class X, class P>
+// BJ: `diag` holds the 3 x 3 inverses of the nodes' diagonal blocks (block
+// Jacobi, mpg_bjacobi_setup_*) and w = Dinv T(r): each lane forms T(r) of its
+// node's three rows from the same sums and applies its own row of the
+// inverse with mpg_bjacobi_apply_*'s arithmetic (products rounded, summed
+// left to right), so w has the bits of that launch run on the plain prologue.
+template <class T, class X, class P, bool BJ = false>
 __global__ __launch_bounds__(kBlock) void k_prologue_rows(const int32_t* __restrict__ blocks, int nblocks,
                                                           const double* __restrict__ rsum,
                                                           const X* __restrict__ x, const X* __restrict__ b,
@@ -175,7 +180,20 @@ __global__ __launch_bounds__(kBlock) void k_prologue_rows(const int32_t* __restr
         T wi = (T)r;
         acc[0] += (double)wi * (double)wi;
         P pw = (P)wi;
-        if (diag) pw = P(0) * pw + P(1) * diag[i] * pw;
+        if constexpr (BJ) {
+#pragma clang fp contract(off)
+            const int q = i / kNodeDof * kNodeDof, kk = i - q;
+            const P* d = diag + (int64_t)q * kNodeDof + kNodeDof * kk;
+            const P own = pw;
+            auto tr = [&](int j) { return j == i ? own : (P)(T)(X)(b[j] - (X)rsum[j]); };
+            pw = d[0] * tr(q);
+            const P p1 = d[1] * tr(q + 1);
+            pw = pw + p1;
+            const P p2 = d[2] * tr(q + 2);
+            pw = pw + p2;
+        } else {
+            if (diag) pw = P(0) * pw + P(1) * diag[i] * pw;
+        }
         wi = (T)pw;
         acc[1] += (double)wi * (double)wi;
         acc[2] += (double)x[i] * (double)x[i];
@@ -574,6 +592,133 @@ __global__ __launch_bounds__(kBlock) void k_step_node(const int32_t* __restrict_
     } else {
         const int t0 = g * tpw, t1 = t0 + tpw < ntiles ? t0 + tpw : ntiles;
         node_tiles<VI, A>(t0, t1, tiles, tiles + ntiles + 1, bptr, recs, nblk, xraw, xfin, pre, epi, prod);
+    }
+}
+
+// ---------------------------------------------------------------- step: SpMV (node blocks) + block Jacobi
+// k_step_node with w = Dinv (A v_k): the 3 x 3 inverse of each node's
+// diagonal block (mpg_bjacobi_setup_*) applied inside the launch. A node's
+// three row sums are formed by three lanes, which may sit in two waves or in
+// two turns of the rows loop (a tile holds up to 3 * 256 rows): every lane
+// keeps P(T(sum)) of its rows in registers until the whole tile has read its
+// products, stores them over the products in LDS, and after a second barrier
+// forms its own row of Dinv * sums -- mpg_bjacobi_apply_*'s arithmetic
+// (products rounded, summed left to right, contraction off) on the values
+// the plain launch would have written: the same bits. The walk over the
+// tiles, the products and the order of every row sum are node_tiles'.
+template <class T, class P, class VI, bool FOLD, class A = double>
+__global__ __launch_bounds__(kBlock) void k_step_node_bj(const int32_t* __restrict__ tiles,
+                                                         const int32_t* __restrict__ bptr,
+                                                         const char* __restrict__ recs,
+                                                         const T* __restrict__ wprev, const T* __restrict__ inv_p,
+                                                         T* __restrict__ V, int64_t ld, int k,
+                                                         const P* __restrict__ dinv, T* __restrict__ w,
+                                                         GivensFold<T> fold, const int8_t* __restrict__ rexp,
+                                                         int ntiles, int64_t nblk, int tpw, int xcd) {
+    constexpr int R = NodeRec<VI>::R;
+    constexpr int D = kNodeDof;
+    __shared__ double prod[kNodeProd];
+    P* xs = reinterpret_cast<P*>(prod);  // (D * kNodeCap values at most: a tile's rows)
+    const T inv = fold_givens<FOLD, T, A>(fold, inv_p);
+    T* __restrict__ Vk = V + (int64_t)k * ld;
+    const int g = xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const int t0 = g * tpw, t1 = t0 + tpw < ntiles ? t0 + tpw : ntiles;
+    const int32_t* __restrict__ tb0 = tiles + ntiles + 1;
+    const int l = threadIdx.x;
+    auto rec = [&](int t) {
+        const int b0 = tb0[t], nb = tb0[t + 1] - b0;
+        int64_t b = (int64_t)b0 + (l < nb ? l : nb - 1);
+        b = b < 0 ? 0 : b >= nblk ? nblk - 1 : b;
+        return recs + b * R;
+    };
+    NodeWords<VI> cur, nxt;
+    cur.load(rec(t0));
+    for (int t = t0; t < t1; ++t) {
+        const int nr0 = tiles[t], nr1 = tiles[t + 1];
+        const int b0 = tb0[t], nb = tb0[t + 1] - b0;
+        const int rows = D * (nr1 - nr0);  // <= D * kNodeCap (node_build)
+        const int c = cur.col();
+        const T r0 = wprev[c], r1 = wprev[c + 1], r2 = wprev[c + 2];
+        const double x0 = (double)(T)(r0 * inv), x1 = (double)(T)(r1 * inv), x2 = (double)(T)(r2 * inv);
+        if (t + 1 < t1) nxt.load(rec(t + 1));
+        if (l < nb) {
+            double* p = prod + l * (D * D);
+#pragma unroll
+            for (int q = 0; q < D; ++q) {
+                p[3 * q + 0] = cur.val(3 * q + 0) * x0;
+                p[3 * q + 1] = cur.val(3 * q + 1) * x1;
+                p[3 * q + 2] = cur.val(3 * q + 2) * x2;
+            }
+        }
+        lds_barrier();
+        P pw[D], dd[D][D];
+        T wp[D];
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+            const int r = l + u * kBlock;
+            pw[u] = P(0);
+            if (r < rows) {
+                const int nr = nr0 + r / D, q = r % D;
+                const int i = D * nr0 + r;
+                const int a = bptr[nr] - b0, z = bptr[nr + 1] - b0;
+                const int e = rexp ? (int)rexp[i] : 0;
+                A acc = A(0);
+                int b = a;
+                for (; b + kNodeSumAhead <= z; b += kNodeSumAhead) {
+                    double v[3 * kNodeSumAhead];
+#pragma unroll
+                    for (int s = 0; s < kNodeSumAhead; ++s) {
+                        const double* p = prod + (b + s) * (D * D) + D * q;
+                        v[3 * s] = p[0];
+                        v[3 * s + 1] = p[1];
+                        v[3 * s + 2] = p[2];
+                    }
+#pragma unroll
+                    for (int s = 0; s < 3 * kNodeSumAhead; ++s) add_prod(acc, v[s]);
+                }
+                for (; b < z; ++b) {
+                    const double* p = prod + b * (D * D) + D * q;
+                    add_prod(acc, p[0]);
+                    add_prod(acc, p[1]);
+                    add_prod(acc, p[2]);
+                }
+                const double sum = acc;
+                pw[u] = (P)(T)ldexp(sum, -e);
+            }
+        }
+        lds_barrier();  // every row sum has read its products
+        // (the lane's rows of the inverses and of w_prev are loaded here, not
+        // held through the row sums, where the registers are needed)
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+            const int r = l + u * kBlock;
+            if (r < rows) {
+                const int i = D * nr0 + r;
+                xs[r] = pw[u];
+                wp[u] = wprev[i];
+#pragma unroll
+                for (int j = 0; j < D; ++j) dd[u][j] = dinv[(int64_t)i * D + j];
+            }
+        }
+        lds_barrier();
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+#pragma clang fp contract(off)
+            const int r = l + u * kBlock;
+            if (r < rows) {
+                const int q0 = r / D * D;
+                const int i = D * nr0 + r;
+                P acc = dd[u][0] * xs[q0];
+                const P p1 = dd[u][1] * xs[q0 + 1];
+                acc = acc + p1;
+                const P p2 = dd[u][2] * xs[q0 + 2];
+                acc = acc + p2;
+                w[i] = (T)acc;
+                Vk[i] = wp[u] * inv;
+            }
+        }
+        lds_barrier();  // the next tile's products overwrite xs
+        cur = nxt;
     }
 }
 
@@ -2063,6 +2208,13 @@ struct mpg_arnoldi {
 };
 
 namespace {
+
+// block Jacobi applied inside the node kernels (desc.block_dinv): 3 x 3
+// blocks on the node-block copy, one GPU's rows (no halo)
+inline bool bj_fused(const mpg_arnoldi* a) {
+    return a->d.block_dinv && a->d.prec_block == kNodeDof && a->node.nblk > 0 && a->d.n % kNodeDof == 0 &&
+           a->front == 0 && a->d.n_ext == a->d.n;
+}
 
 // combos: 0 baseline <d,d,d,d>; 1 single-prec <d,d,f,d>; 2 single <f,f,f,f>;
 //         3 mixed <f,d,f,f>; 4 mixed-half <f,d,f,h>

@@ -169,6 +169,18 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
                              node_xcd(S));
                 return (int)MPG_OK;
             };
+            if (bj_fused(a)) {  // block Jacobi inside the launch (k_step_node_bj takes the inverses as `diag`)
+                auto gobj = [&](auto kern) {
+                    launch_timed(a->ctx, kern, dim3((S.ntiles + tpw - 1) / tpw), dim3(kBlock),
+                                 static_cast<const int32_t*>(S.tiles), static_cast<const int32_t*>(S.bptr),
+                                 static_cast<const char*>(S.recs), static_cast<const T*>(a->w[k & 1]),
+                                 static_cast<const T*>(a->inv()), static_cast<T*>(a->V), a->ld, k,
+                                 static_cast<const P*>(a->d.block_dinv), static_cast<T*>(a->w[(k + 1) & 1]), gf,
+                                 a->d.inner_row_exp, S.ntiles, S.nblk, tpw, node_xcd(S));
+                    return (int)MPG_OK;
+                };
+                return fold ? gobj(k_step_node_bj<T, P, VI, true, A>) : gobj(k_step_node_bj<T, P, VI, false, A>);
+            }
             if (tpw > 1) return fold ? go(k_step_node<T, P, VI, true, true, A>) : go(k_step_node<T, P, VI, false, true, A>);
             return fold ? go(k_step_node<T, P, VI, true, false, A>) : go(k_step_node<T, P, VI, false, false, A>);
         }

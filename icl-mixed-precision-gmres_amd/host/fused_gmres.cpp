@@ -137,7 +137,7 @@ struct FusedEngine::Impl {
 
     // step k runs the SpMV and the dots in one launch
     // (one GPU, plain CGS whose update sums the dots' partials itself, no ILU between the launches)
-    bool step_dots_engine_ok() const { return !(comm || ilu || orth != MPG_ORTH_CGS || !cgs_partials || combine); }
+    bool step_dots_engine_ok() const { return !(comm || sep_prec() || orth != MPG_ORTH_CGS || !cgs_partials || combine); }
     bool step_dots_at(int k) const {
         if (step_dots == 0) return false;
         if (step_dots == 2) return true;  // (an unsupported step is then an error at its launch)
@@ -161,6 +161,23 @@ struct FusedEngine::Impl {
     int64_t stamp_cap = 0, stamp_q = 0, stamp_max = 0;  // waves per launch, launches armed, launch slots
     std::vector<int32_t> rowptr_host;
     mpg_ilu_t ilu = nullptr;  // ILU(0) factors (prec ilu / ilu_jacobi), applied between phase kernels
+    // block Jacobi (prec bjacobi): bs x bs inverses of the nodes' diagonal blocks in the
+    // preconditioner precision (mpg_bjacobi_setup_*), applied by a launch of
+    // its own in the slot ILU's solves take
+    int bj_bs = 0;  // unknowns per node; 0: another preconditioner
+    DevMem bj_dinv;
+    // MPG_BJACOBI_FUSE=1: the Arnoldi SpMV / the residual prologue apply the
+    // inverses themselves where the storage supports it (mpg_arnoldi_prec_fused:
+    // node blocks, bs = 3; the same bits). Unset or 0: the launch of its own,
+    // the faster form as measured -- C4 stand-in, mixed CGS: 454 us per step
+    // against 540 fused (k_step_node_bj holds 80 VGPRs where k_step_node holds
+    // 54: 6 waves per SIMD instead of 8), point Jacobi 451
+    // (profiles/r08_bjacobi/bjacobi_bench.json)
+    bool bj_fused_step = false, bj_fused_prologue = false;
+    // a preconditioner applied between the phase kernels, not inside them
+    bool sep_prec() const { return ilu || bj_bs; }
+    bool sep_prec_step() const { return ilu || (bj_bs && !bj_fused_step); }
+    bool sep_prec_prologue() const { return ilu || (bj_bs && !bj_fused_prologue); }
     bool orthloss = false;    // LostOrthogonality: v_{k+1} stored each step, S / u below
     DevMem loss_S, loss_u;    // (m+1) x (m+1) and m+2 of T, zero-filled (IterUtil.hpp:185-191)
 
@@ -197,9 +214,19 @@ struct FusedEngine::Impl {
         check(mpg_memcpy_d2h(ctx, &h, acc, sizeof h), "d2h", ctx);
         return h;
     }
-    // M^-1 w for the ILU preconditioners, with typesafe_apply's casts when
-    // the preconditioner precision differs (gmres.cpp:12-22)
+    // x <- Dinv x on a vector of T (the casts to and from P inside the launch)
+    void apply_bjacobi(void* w) {
+        int st;
+        if (ty.T == MPG_F32) st = mpg_bjacobi_apply_f32(ctx, n, bj_bs, bj_dinv.as<float>(), (float*)w);
+        else if (ty.P == MPG_F64) st = mpg_bjacobi_apply_f64(ctx, n, bj_bs, bj_dinv.as<double>(), (double*)w);
+        else st = mpg_bjacobi_apply_f64_p32(ctx, n, bj_bs, bj_dinv.as<float>(), (double*)w);
+        check(st, "block Jacobi apply", ctx);
+    }
+    // M^-1 w for the preconditioners applied between the phase kernels: block
+    // Jacobi, or ILU with typesafe_apply's casts when the preconditioner
+    // precision differs (gmres.cpp:12-22)
     void apply_ilu(void* w) {
+        if (bj_bs) return apply_bjacobi(w);
         void* wp = w;
         if (ty.P != ty.T) {
             cast(w, ty.T, tmp_p.p, ty.P, n);
@@ -237,7 +264,20 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     const bool ilu = a.prec == MPG_PREC_ILU || a.prec == MPG_PREC_ILU_JACOBI;
     if (ilu && comm)
         throw std::invalid_argument("ILU / ILU-Jacobi factor the whole matrix: not available on a row-partitioned solve");
-    if (!ilu && a.prec != MPG_PREC_IDENTITY && a.prec != MPG_PREC_JACOBI) throw std::invalid_argument("Unknown prec type");
+    const bool bjacobi = a.prec == MPG_PREC_BLOCK_JACOBI;
+    if (!ilu && !bjacobi && a.prec != MPG_PREC_IDENTITY && a.prec != MPG_PREC_JACOBI)
+        throw std::invalid_argument("Unknown prec type");
+    if (bjacobi) {
+        const int bs = a.prec_block == 0 ? 3 : a.prec_block;
+        if (bs < 2 || bs > 4) throw std::invalid_argument("prec bjacobi: prec_block must be 2, 3 or 4 (0: 3)");
+        if (comm)
+            throw std::invalid_argument("prec bjacobi is not available on a row-partitioned solve (a rank's diagonal "
+                                        "blocks are not set up across the partition)");
+        if (a.n % bs != 0)
+            throw std::invalid_argument("prec bjacobi: n = " + std::to_string(a.n) + " is not a multiple of the block size " +
+                                        std::to_string(bs));
+        I.bj_bs = bs;
+    }
     I.orthloss = a.orthloss && a.rtol != 0 && !a.repeat_iter;  // alloc_convergence order (gmres_perf_test.cpp:184-195)
     if (I.orthloss && comm)
         throw std::invalid_argument("LostOrthogonality restarts are not available on a row-partitioned solve");
@@ -318,6 +358,21 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
         }
     }
 
+    // block Jacobi in the preconditioner precision, from the matrix Jacobi<P>
+    // takes above: the fp64 A for P = double, else its fp32 copy
+    if (I.bj_bs) {
+        I.bj_dinv = DevMem(ctx, (size_t)I.n * I.bj_bs * dsize(ty.P) + 16);
+        int st;
+        if (ty.P == MPG_F64) {
+            st = mpg_bjacobi_setup_f64(ctx, I.csr, I.val64.as<double>(), I.bj_bs, I.bj_dinv.as<double>(), nullptr);
+        } else {
+            DevMem f32(ctx, std::max<size_t>(nz, 1) * 4);
+            I.cast(I.val64.p, MPG_F64, f32.p, MPG_F32, (int64_t)nz);
+            st = mpg_bjacobi_setup_f32(ctx, I.csr, f32.as<float>(), I.bj_bs, I.bj_dinv.as<float>(), nullptr);
+        }
+        check(st, "block Jacobi set-up", ctx);
+    }
+
     // ILU(0) of the fp64 A in the preconditioner precision (gmres_perf_test.cpp:70-79, 140-149)
     if (ilu) check(mpg_ilu0_create(ctx, I.csr, I.val64.as<double>(), ty.P == MPG_F64 ? 0 : 1, &I.ilu), "ilu0", ctx);
 
@@ -351,6 +406,7 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
         }
         if (I.ilu) I.solve_ilu(wp);
         if (ty.P != ty.T) I.cast(I.tmp_p.p, ty.P, I.tmp_t.p, ty.T, I.n);
+        if (I.bj_bs) I.apply_bjacobi(I.tmp_t.p);  // (on the vector of T, casting inside)
         minvb_norm = I.nrm2(I.tmp_t.p, ty.T, I.n);
     }
     // ||A||_F of the matrix the driver was given (A_single in mixed mode)
@@ -386,9 +442,18 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     d.x = I.xp;
     d.spmv_format = a.spmv_format;
     d.n_front = n_front;
+    {
+        const char* benv = std::getenv("MPG_BJACOBI_FUSE");
+        if (I.bj_bs && benv && *benv == '1') {
+            d.block_dinv = I.bj_dinv.p;
+            d.prec_block = I.bj_bs;
+        }
+    }
     // rows all in range: the unscaled kernels (no exponent loads, same bits)
     d.inner_row_exp = I.half_stats[0] > 0 ? I.row_exp.as<int8_t>() : nullptr;
     check(mpg_arnoldi_create(ctx, &d, &I.arn), "mpg_arnoldi_create", ctx);
+    I.bj_fused_step = mpg_arnoldi_prec_fused(I.arn, 0) == 1;
+    I.bj_fused_prologue = mpg_arnoldi_prec_fused(I.arn, 1) == 1;
     // fp32 Arnoldi: the reference's fp32 accumulation class on request (arnoldi.h)
     if (a.accum) check(mpg_arnoldi_set_accum(I.arn, MPG_ACCUM_F32), "mpg_arnoldi_set_accum", ctx);
     // ranks all-reduce per-workgroup partials in place: same count on every rank
@@ -497,8 +562,10 @@ void FusedEngine::prologue() {
     if (I.comm) I.comm->halo(I.xp, (int)dsize(I.ty.X), I.stream());
     timed(1, [&] { check(mpg_arnoldi_prologue(I.arn), "prologue", I.ctx); });
     check(mpg_arnoldi_prologue(I.arn), "prologue", I.ctx);
-    if (I.ilu) {  // w = M(T(r)) outside the kernel, then ||w||^2 again
-        I.apply_ilu(mpg_arnoldi_wprev_dev(I.arn, 0));
+    if (I.sep_prec()) {  // w = M(T(r)) outside the kernel, then ||w||^2 again
+        // (block Jacobi inside the prologue: only the norm, in the order the
+        // separate form sums it, so both forms give one beta)
+        if (I.sep_prec_prologue()) I.apply_ilu(mpg_arnoldi_wprev_dev(I.arn, 0));
         check(mpg_arnoldi_prologue_wnorm(I.arn), "prologue wnorm", I.ctx);
     }
     if (!I.comm) {  // the 3 column sums inside the finish launch (same bits)
@@ -543,7 +610,7 @@ void FusedEngine::givens(int k) {
 void FusedEngine::step(int k, bool fold) {
     Impl& I = *p_;
     // SpMV and panel dots in one launch (one GPU, CGS with in-launch sums)
-    if (I.fuse_dots && !I.comm && !I.ilu && I.orth == MPG_ORTH_CGS && I.cgs_partials && !I.combine &&
+    if (I.fuse_dots && !I.comm && !I.sep_prec() && I.orth == MPG_ORTH_CGS && I.cgs_partials && !I.combine &&
         k + 1 <= I.fuse_dots_k0) {
         timed(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
         const int st = mpg_arnoldi_spmv_dots(I.arn, k, fold && k > 0 ? 2 : 0);
@@ -562,7 +629,8 @@ void FusedEngine::step(int k, bool fold) {
         const int f = fold && k > 0 ? 2 : 0;
         if (!I.step_dots_engine_ok())
             throw StatusError(MPG_ERR_UNSUPPORTED, "MPG_STEP_DOTS=2: the SpMV + dots launch needs one GPU and plain CGS "
-                                                   "with in-launch sums, without ILU");
+                                                   "with in-launch sums, without a preconditioner launch (ILU, "
+                                                   "block Jacobi) between the SpMV and the dots");
         timed(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
         const int st = mpg_arnoldi_step_dots(I.arn, k, f);
         if (st == MPG_OK) {
@@ -609,7 +677,7 @@ void FusedEngine::step(int k, bool fold) {
         dup(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
         timed_end(0);
     }
-    if (I.ilu) I.apply_ilu(mpg_arnoldi_wprev_dev(I.arn, k + 1));  // w = M(A v_k)
+    if (I.sep_prec_step()) I.apply_ilu(mpg_arnoldi_wprev_dev(I.arn, k + 1));  // w = M(A v_k)
     if (I.orth == MPG_ORTH_MGS) {
         check(mpg_arnoldi_dots(I.arn, k), "dots", I.ctx);
         if (!I.comm) {  // one GPU: each update sums the previous launch's partials itself
@@ -1027,7 +1095,10 @@ double FusedEngine::phase_bytes(int which) const {
     const Impl& I = *p_;
     const double n = I.n, z = (double)I.nnz, sT = (double)dsize(I.ty.T), sX = (double)dsize(I.ty.X);
     const double sV = (double)dsize(I.ty.VI), sP = (double)dsize(I.ty.P);
-    const double jac = I.args.prec == MPG_PREC_JACOBI ? 1.0 : 0.0;
+    // Jacobi's diagonal read inside the launch; block Jacobi's own launch
+    // after it (w read and written again, bs inverse entries per row)
+    const bool bjf = which == 1 ? I.bj_fused_prologue : I.bj_fused_step;
+    const double jac = I.args.prec == MPG_PREC_JACOBI ? 1.0 : I.bj_bs ? (bjf ? 0.0 : 2 * sT / sP) + I.bj_bs : 0.0;
     if (which == 0) {
         // SURVEY §8(d) B_spmv, the same for every storage: CSR values + int32
         // columns + row pointers, x read once, y written (the SELL-64 copy
@@ -1071,6 +1142,7 @@ double FusedEngine::phase_bytes(int which) const {
 mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
 bool FusedEngine::givens_folded() const { return p_->fold; }
+int FusedEngine::prec_fused() const { return p_->bj_bs ? (p_->bj_fused_step ? 1 : 0) : -1; }
 int FusedEngine::step_dots_steps() const { return p_->step_dots_steps(); }
 int FusedEngine::step_dots_status(int k) const { return mpg_arnoldi_step_dots_supported(p_->arn, k); }
 
@@ -1622,6 +1694,7 @@ int mpg_engine_sell_columns(mpg_engine_t e, int32_t* form, int64_t* csr_slices, 
     return mpg_arnoldi_sell_columns(e->eng->arnoldi(), form, csr_slices, implicit_slices);
 }
 
+int mpg_engine_prec_fused(mpg_engine_t e) { return e && e->eng ? e->eng->prec_fused() : -1; }
 int mpg_engine_accum(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return mpg_arnoldi_accum(e->eng->arnoldi());

@@ -104,6 +104,7 @@ public:
     const int64_t* half_stats() const;
     // the Givens step rides the next SpMV (MPG_FOLD_GIVENS, mpg_arnoldi_fold_pays)
     bool givens_folded() const;
+    int prec_fused() const;  // mpg_engine_prec_fused
     int step_dots_steps() const;       // steps of a cycle that run the SpMV inside the dots' launch
     int step_dots_status(int k) const;  // mpg_arnoldi_step_dots_supported at step k
     void sync();

@@ -11,7 +11,8 @@
 // stencil27:NX[:DOF[:SEED]] (synthetic input instead of --Apath,
 // mpg_gen_spec), --mode mixed-half, --half-unscaled (mixed-half: plain fp16
 // cast, a value outside fp16's range is an error), --engine {fused,surface},
-// --device D, --stop-on-breakdown (end the solve with an error at the first
+// --prec bjacobi [--prec-block {2,3,4}] (the inverse of each node's diagonal
+// block; 3 unknowns per node unless told), --device D, --stop-on-breakdown (end the solve with an error at the first
 // non-finite Arnoldi residual; without it the count goes to stderr),
 // --ngpus N (row-partition the fused solve over N GPUs of this process, one
 // host thread per GPU, RCCL clique by ncclCommInitAll: mpg_solve_multi_gpu;
@@ -75,6 +76,7 @@ int main(int argc, char* argv[]) {
         else if (f == "--max-restarts") a.max_restarts = std::stol(next());
         else if (f == "--rand") rand_seed = (unsigned)std::stoi(next());
         else if (f == "--jacobi-steps") a.jacobi_steps = std::stoi(next());
+        else if (f == "--prec-block") a.prec_block = std::stoi(next());
         else if (f == "--gpu") { /* always on the GPU */ }
         else if (f == "--device") a.device = std::stoi(next());
         else if (f == "--ngpus") ngpus = std::stoi(next());
@@ -106,6 +108,7 @@ int main(int argc, char* argv[]) {
             else if (v == "identity") a.prec = MPG_PREC_IDENTITY;
             else if (v == "jacobi") a.prec = MPG_PREC_JACOBI;
             else if (v == "ilu_jacobi") a.prec = MPG_PREC_ILU_JACOBI;
+            else if (v == "bjacobi") a.prec = MPG_PREC_BLOCK_JACOBI;
             else { std::cout << "Unknown Preconditioner" << std::endl; return 1; }
         } else if (f == "--engine") {
             const std::string v = next();

@@ -158,4 +158,29 @@ public:
     void apply(Vect<Type, Device> rhs) override { gdmv(1.0, diag_, rhs, 0.0, rhs); }
 };
 
+// backend primitives: the inverses of A's bs x bs diagonal blocks (bs*bs
+// values per block, row-major), and x <- blockdiag(dinv) x in place
+template <class Type, class Device>
+void bjacobi_setup(SparseMatrix<Type, Device> A, int bs, Vect<Type, Device> dinv);
+template <class Type, class Device>
+void bjacobi_apply(int bs, Vect<Type, Device> dinv, Vect<Type, Device> x);
+
+// Block-Jacobi preconditioner M = blockdiag(D_r)^-1 for matrices ordered by
+// node, bs = 2, 3 or 4 unknowns per node (an addition to the reference's
+// set): built from A in the preconditioner precision, as Jacobi is.
+template <class Type, class Device>
+class BlockJacobi : public LinearOperator<Type, Device> {
+    int bs_;
+    Vect<Type, Device> dinv_;
+
+public:
+    BlockJacobi(SparseMatrix<Type, Device> A, int bs) : bs_(bs), dinv_((size_t)A.nrows() * (size_t)bs) {
+        bjacobi_setup(A, bs_, dinv_);
+    }
+    int n() const { return (int)(dinv_.n() / (size_t)bs_); }
+    int block() const { return bs_; }
+    Vect<Type, Device> dinv_vect() { return dinv_; }
+    void apply(Vect<Type, Device> rhs) override { bjacobi_apply(bs_, dinv_, rhs); }
+};
+
 #endif  // MPGMRES_KERNELS_HPP

@@ -1129,6 +1129,24 @@ template <> void jacobi_diag<double, Hip>(SparseMatrix<double, Hip> A, Vect<doub
 template <> void jacobi_diag<float, Hip>(SparseMatrix<float, Hip> A, Vect<float, Hip> d) {
     check(mpg_jacobi_setup_f32(C, A.csr(), A.vals_data(), d.data()), "jacobi setup");
 }
+// block Jacobi: like every surface write, the apply takes the context
+// through current_ctx() -- deferred work is issued first, the write count of
+// the host-norm memo moves on, and the launch lands on the context's stream,
+// where a cycle program records it
+template <> void bjacobi_setup<double, Hip>(SparseMatrix<double, Hip> A, int bs, Vect<double, Hip> d) {
+    check(mpg_bjacobi_setup_f64(C, A.csr(), A.vals_data(), bs, d.data(), nullptr), "block Jacobi set-up");
+}
+template <> void bjacobi_setup<float, Hip>(SparseMatrix<float, Hip> A, int bs, Vect<float, Hip> d) {
+    check(mpg_bjacobi_setup_f32(C, A.csr(), A.vals_data(), bs, d.data(), nullptr), "block Jacobi set-up");
+}
+template <> void bjacobi_apply<double, Hip>(int bs, Vect<double, Hip> d, Vect<double, Hip> x) {
+    assert(d.n() == x.n() * (size_t)bs);
+    check(mpg_bjacobi_apply_f64(C, (int64_t)x.n(), bs, d.data(), x.data()), "block Jacobi apply");
+}
+template <> void bjacobi_apply<float, Hip>(int bs, Vect<float, Hip> d, Vect<float, Hip> x) {
+    assert(d.n() == x.n() * (size_t)bs);
+    check(mpg_bjacobi_apply_f32(C, (int64_t)x.n(), bs, d.data(), x.data()), "block Jacobi apply");
+}
 
 // ---- ILU(0) / ILU-Jacobi (kernels_mkl.cpp:355-506, kernels_cuda.cpp:617-791) ----
 namespace {

@@ -45,8 +45,16 @@ std::unique_ptr<Convergence<T, Hip>> make_convergence(const mpg_solve_args& a) {
 // converted to the preconditioner precision)
 template <class P>
 std::unique_ptr<LinearOperator<P, Hip>> make_preconditioner(int prec, const SparseMatrix<double, Hip>& A,
-                                                            int jacobi_steps) {
+                                                            int jacobi_steps, int prec_block) {
     switch (prec) {
+        case MPG_PREC_BLOCK_JACOBI: {
+            const int bs = prec_block == 0 ? 3 : prec_block;
+            if (bs < 2 || bs > 4) throw std::invalid_argument("prec bjacobi: prec_block must be 2, 3 or 4 (0: 3)");
+            if (A.nrows() % bs != 0)
+                throw std::invalid_argument("prec bjacobi: n = " + std::to_string(A.nrows()) +
+                                            " is not a multiple of the block size " + std::to_string(bs));
+            return std::make_unique<BlockJacobi<P, Hip>>(A, bs);
+        }
         case MPG_PREC_IDENTITY: return std::make_unique<Identity<P, Hip>>();
         case MPG_PREC_JACOBI: return std::make_unique<Jacobi<P, Hip>>(A);
         case MPG_PREC_ILU: return std::make_unique<ILU<P, Hip>>(ilu0<P, Hip>(A));
@@ -112,7 +120,7 @@ void do_baseline(const mpg_solve_args& a, const SparseMatrix<double, Hip>& A, Ve
     // fp32-rounded copy, widened back for Type = double.
     const SparseMatrix<float, Hip> A_f32(A);
     const SparseMatrix<Type, Hip> A_type(A_f32);
-    auto M = make_preconditioner<PrecType>(a.prec, A, a.jacobi_steps);
+    auto M = make_preconditioner<PrecType>(a.prec, A, a.jacobi_steps, a.prec_block);
     Hip::fence();
     const double prec_s = seconds_since(t0);
 
@@ -145,7 +153,7 @@ void do_mixed(const mpg_solve_args& a, const SparseMatrix<double, Hip>& A, Vect<
     Vect<double, Hip> x(n);
     auto t0 = clk::now();
     const SparseMatrix<float, Hip> A_single(A);
-    auto M = make_preconditioner<float>(a.prec, A, a.jacobi_steps);
+    auto M = make_preconditioner<float>(a.prec, A, a.jacobi_steps, a.prec_block);
     Hip::fence();
     const double prec_s = seconds_since(t0);
 

@@ -67,6 +67,11 @@ typedef struct {
     int32_t n_front;       /* halo rows of lower ranks, local ids [-n_front, 0) (0 on one GPU) */
     const int8_t* inner_row_exp; /* inner_val MPG_F16: per-row exponents of the scaled fp16 copy
                                     (mpg_csr_half_values, capi.h), or NULL (unscaled) */
+    const void* block_dinv; /* block Jacobi applied inside the launches: the inverses of the diagonal
+                               blocks (mpg_bjacobi_setup_*, prec_type), or NULL. Taken where the storage
+                               supports it (mpg_arnoldi_prec_fused); the caller applies it in a launch of
+                               its own elsewhere (mpg_bjacobi_apply_*, then mpg_arnoldi_prologue_wnorm) */
+    int32_t prec_block;     /* ... unknowns per block (fused: 3, on node blocks) */
 } mpg_arnoldi_desc;
 
 /* Entries allocated in front of row 0 of every vector with a halo (x, the
@@ -79,6 +84,10 @@ typedef struct {
  * H, Givens state, two w buffers (n_ext), partials and the report block. */
 int mpg_arnoldi_create(mpg_ctx_t ctx, const mpg_arnoldi_desc* desc, mpg_arnoldi_t* out);
 int mpg_arnoldi_destroy(mpg_arnoldi_t a);
+/* desc.block_dinv: 1 when the launches of `which` (0: the Arnoldi SpMV of every step, 1: the
+ * residual prologue) apply the block inverses themselves -- node-block storage, 3 x 3 blocks -- with
+ * the bits of mpg_bjacobi_apply_* on their output; 0 when the caller has to apply them */
+int mpg_arnoldi_prec_fused(mpg_arnoldi_t a, int which);
 
 /* Storage the Arnoldi SpMV runs on: *format 1 = CSR row blocks (cuSPARSE
  * csrmv's input, types_cuda.hpp:53-60), 2 = SELL-64 copy made at create

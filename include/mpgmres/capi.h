@@ -431,6 +431,30 @@ int mpg_jacobi_rowmax_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, double*
 int mpg_jacobi_diag_f64(mpg_ctx_t ctx, mpg_csr_t A, const double* vals, const double* rowmax_dev, double* diag_out);
 int mpg_jacobi_diag_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, const double* rowmax_dev, float* diag_out);
 
+/* ---- block Jacobi (bjacobi.hip): M = blockdiag(D_r)^-1 for bs = 2, 3 or 4
+ * unknowns per node, rows % bs == 0 (else MPG_ERR_ARG). D_r is rows and
+ * columns [bs r, bs r + bs) of A: a missing entry is 0, the first occurrence
+ * of a column wins. The block's values are widened to fp64 and inverted by
+ * Gauss-Jordan on [D | I] with partial pivoting (largest |entry| of the
+ * column, lowest row on a tie; row c divided by the pivot, then
+ * row q -= M[q][c] * row c for q = 0..bs-1, q != c, product and difference
+ * each rounded), and the inverse is rounded once to the values' precision:
+ * dinv_out holds bs*bs values per block, row-major, blocks contiguous
+ * (rows * bs values). A block with a zero or non-finite pivot fails the
+ * set-up: MPG_ERR_BREAKDOWN, the lowest such block in *first_bad_block (-1
+ * otherwise; may be NULL) and named in mpg_ctx_last_error. Synchronises. */
+int mpg_bjacobi_setup_f64(mpg_ctx_t ctx, mpg_csr_t A, const double* vals, int32_t bs, double* dinv_out,
+                          int32_t* first_bad_block);
+int mpg_bjacobi_setup_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, int32_t bs, float* dinv_out,
+                          int32_t* first_bad_block);
+/* x <- M x in place on a device vector of n rows (n % bs == 0): per block
+ * y_i = sum_j dinv[i][j] * x_j in the precision of dinv, each product rounded
+ * and summed left to right in j; _f64_p32 casts x to float before and the
+ * result back after (mode single-prec). One launch, coalesced. */
+int mpg_bjacobi_apply_f64(mpg_ctx_t ctx, int64_t n, int32_t bs, const double* dinv, double* x);
+int mpg_bjacobi_apply_f32(mpg_ctx_t ctx, int64_t n, int32_t bs, const float* dinv, float* x);
+int mpg_bjacobi_apply_f64_p32(mpg_ctx_t ctx, int64_t n, int32_t bs, const float* dinv, double* x);
+
 #ifdef __cplusplus
 }
 #endif

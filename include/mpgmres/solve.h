@@ -32,7 +32,13 @@ typedef enum {
 typedef enum { MPG_ORTH_CGS = 0, MPG_ORTH_MGS = 1, MPG_ORTH_CGSR = 2 } mpg_orth_t;
 
 /* gmres_perf_test.cpp:24-29 prec_t (same numbering) */
-typedef enum { MPG_PREC_ILU = 0, MPG_PREC_ILU_JACOBI = 1, MPG_PREC_JACOBI = 2, MPG_PREC_IDENTITY = 3 } mpg_prec_t;
+typedef enum {
+    MPG_PREC_ILU = 0,
+    MPG_PREC_ILU_JACOBI = 1,
+    MPG_PREC_JACOBI = 2,
+    MPG_PREC_IDENTITY = 3,
+    MPG_PREC_BLOCK_JACOBI = 4 /* new: the inverse of each node's diagonal block (mpg_bjacobi_*, capi.h) */
+} mpg_prec_t;
 
 typedef enum {
     MPG_ENGINE_SURFACE = 0,  /* generic driver over the kernels.hpp operator surface */
@@ -75,6 +81,9 @@ typedef struct {
                               the class of the reference's cblas_s* / mkl_sparse_s_mv (--accum f32);
                               fused engine only (the operator surface refuses it: MPG_ERR_UNSUPPORTED);
                               ignored by an fp64 Arnoldi and by the oracle */
+    int32_t prec_block;    /* MPG_PREC_BLOCK_JACOBI: unknowns per node, 2, 3 or 4 (0: 3; anything else
+                              MPG_ERR_ARG); n must be a multiple of it. Appended last: a caller compiled
+                              against the struct without it (the oracle) reads the same layout */
 } mpg_solve_args;
 
 typedef struct {
@@ -183,6 +192,9 @@ int mpg_engine_givens_folded(mpg_engine_t e);
  * support check gives at step k (MPG_OK / MPG_ERR_UNSUPPORTED) */
 int mpg_engine_step_dots_steps(mpg_engine_t e);
 int mpg_engine_step_dots_status(mpg_engine_t e, int k);
+/* block Jacobi: 1 when the apply runs inside the SpMV / residual launches, 0 when it is a
+ * launch of its own between them and the dots; -1 for every other preconditioner */
+int mpg_engine_prec_fused(mpg_engine_t e);
 /* the accumulation class the engine's Arnoldi runs: MPG_ACCUM_F64 0 / MPG_ACCUM_F32 1 (arnoldi.h) */
 int mpg_engine_accum(mpg_engine_t e);
 /* the residual prologue's storage (mpg_arnoldi_prologue_format: 1 CSR, 2 SELL, 3 node blocks) */
