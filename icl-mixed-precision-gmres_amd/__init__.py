@@ -22,8 +22,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (ACCUMS, ENGINES, MODES, ORTHS, PRECS, SPMV_FORMATS, STATUS, CondestResult, HostCsr, RankLayout, SolveArgs, SolveResult,
-                   condest_args, condest_dict)
+from ._abi import (ACCUMS, ENGINES, MODES, ORTHS, PRECS, SPMV_FORMATS, STATUS, CondestResult, CyclePolicy, HostCsr, RankLayout, SolveArgs,
+                   SolveResult, condest_args, condest_dict)
 
 PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
@@ -206,6 +206,8 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_givens_folded.argtypes = [C.c_void_p]
     lib.mpg_engine_step_dots_steps.argtypes = [C.c_void_p]
     lib.mpg_engine_step_dots_status.argtypes = [C.c_void_p, C.c_int]
+    lib.mpg_engine_cycle_policy.argtypes = [C.c_void_p, C.POINTER(CyclePolicy)]
+    lib.mpg_cycle_plan_describe.argtypes = [C.POINTER(CyclePolicy), C.c_char_p, C.c_int]
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_fused.argtypes = [C.c_void_p]
     lib.mpg_engine_prologue_format.argtypes = [C.c_void_p]
@@ -931,6 +933,14 @@ class Engine:
         the SpMV can run inside the dots' launch; MPG_ERR_UNSUPPORTED, -5:
         it cannot), without launching (mpg_engine_step_dots_status)."""
         return int(self._lib.mpg_engine_step_dots_status(self._h, k))
+
+    def cycle_policy(self) -> CyclePolicy:
+        """What decides the launches of this engine's restart cycle, as resolved
+        at its creation (mpg_engine_cycle_policy)."""
+        p = CyclePolicy()
+        if self._lib.mpg_engine_cycle_policy(self._h, C.byref(p)):
+            raise RuntimeError("mpg_engine_cycle_policy failed")
+        return p
 
     def sell_columns(self) -> dict:
         """Column form of the Arnoldi SpMV's SELL copy (mpg_engine_sell_columns):

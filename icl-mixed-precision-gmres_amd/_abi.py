@@ -149,3 +149,17 @@ class RankLayout(C.Structure):
         ("device", C.c_int32),
         ("transport_ranks", C.c_int32),
     ]
+
+
+CYCLE_POLICY_STEPS = 128  # MPG_CYCLE_POLICY_STEPS
+
+
+class CyclePolicy(C.Structure):
+    """mpg_cycle_policy (solve.h): what decides the launches of a restart cycle."""
+    _fields_ = [(f, C.c_int32) for f in (
+        "ranks", "orth", "m", "graph", "pipeline", "fold", "combine", "cgs_partials", "fuse_dots",
+        "fuse_dots_required", "fuse_dots_k0", "step_dots", "step_dots_lo", "step_dots_hi", "sep_prec",
+        "sep_prec_step", "sep_prec_prologue", "partials_max_cols", "fold_max_m")] + [
+        ("step_dots_ok", C.c_uint8 * CYCLE_POLICY_STEPS),
+        ("spmv_dots_ok", C.c_uint8 * CYCLE_POLICY_STEPS),
+    ]

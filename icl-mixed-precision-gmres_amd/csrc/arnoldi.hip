@@ -370,6 +370,9 @@ int mpg_arnoldi_spmv_dots(mpg_arnoldi_t a, int k, int fold) {
     if (fold < 0 || fold > 2) return MPG_ERR_ARG;
     return spmv_impl(a, k, fold, true);
 }
+int mpg_arnoldi_spmv_dots_supported(mpg_arnoldi_t a, int k) {
+    return a && a->acc32 ? mpg_acc32::spmv_dots_ok(a, k) : spmv_dots_check<double>(a, k);
+}
 int mpg_arnoldi_step_dots(mpg_arnoldi_t a, int k, int fold) {
     return a && a->acc32 ? mpg_acc32::step_dots(a, k, fold) : step_dots_run<double>(a, k, fold);
 }

@@ -483,7 +483,7 @@ struct GivensFold {
 // the SpMVs, whose occupancy sits on VGPR thresholds, even this uniform
 // branch cost up to 20 VGPRs (C4's stepped kernel 71 -> 91, -11 % in time),
 // and a branch-free form with a sink word slowed the BAND SpMV; the SpMV is
-// timed by duplicate launches instead (time_phase_dup, host/fused_gmres.cpp).
+// timed by duplicate launches instead (time_phase_dup, host/fused_timing.cpp).
 // Round 5: a compile-time choice. The product instantiations
 // (STAMP = false) hold no stamp code at all; the launch sites pick the STAMP
 // = true instantiation only for a launch that mpg_arnoldi_stamp_next armed.

@@ -52,12 +52,21 @@ int reduce_run(mpg_arnoldi_t a, int ncols) {
 constexpr int kStepSellBlock = MPG_STEP_SELL_BLOCK;
 using kBlockC = std::integral_constant<int, kBlock>;
 
+// the status spmv_run(a, k, fold, dots = true) returns ahead of its launch
+template <class A>
+int spmv_dots_check(const mpg_arnoldi* a, int k) {
+    if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
+    if (!std::is_same_v<A, double> || a->d.n <= 0 || a->sell.nslices == 0 || !a->sell.c16 || !a->sell.win ||
+        (a->combo != 2 && a->combo != 3) || k + 1 > kNC || a->d.orth == kOrthMGS)
+        return MPG_ERR_UNSUPPORTED;
+    return MPG_OK;
+}
+
 template <class A>
 int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
     if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
-    if (dots && (!std::is_same_v<A, double> || a->d.n <= 0 || a->sell.nslices == 0 || !a->sell.c16 || !a->sell.win ||
-                 (a->combo != 2 && a->combo != 3) || k + 1 > kNC || a->d.orth == kOrthMGS))
-        return MPG_ERR_UNSUPPORTED;
+    if (dots)
+        if (int st = spmv_dots_check<A>(a, k)) return st;
     if (fold && (k < 1 || a->d.m > kFoldMaxM)) return MPG_ERR_ARG;
     const mpg_csr* Acsr = a->d.A;
     int st = dispatch_acc<A>(a->combo, [&](auto t, auto, auto p, auto vi) {
@@ -547,6 +556,7 @@ int reduce(mpg_arnoldi* a, int ncols);
 int spmv(mpg_arnoldi* a, int k, int fold, bool dots);
 int step_dots(mpg_arnoldi* a, int k, int fold);
 int step_dots_ok(const mpg_arnoldi* a, int k);
+int spmv_dots_ok(const mpg_arnoldi* a, int k);
 int dots(mpg_arnoldi* a, int k, bool combine);
 int cgs(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool no_next);
 int mgs(mpg_arnoldi* a, int k, int j, bool from_partials);

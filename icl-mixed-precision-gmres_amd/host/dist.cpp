@@ -630,7 +630,7 @@ int solve_rank_threads(const mpg_solve_args* a, int32_t P, mpg_solve_result* r, 
                         L.n_ext = mpg_halo_n_ext(plans[q]);
                         L.row0 = r0;
                         L.half_rows_scaled = e.half_stats()[0];
-                        L.givens_folded = e.givens_folded() ? 1 : 0;
+                        L.givens_folded = e.policy().fold;
                         L.device = devices[(size_t)q];
                         L.transport_ranks = comm->transport_ranks();
                     }

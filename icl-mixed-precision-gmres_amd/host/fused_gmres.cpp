@@ -33,13 +33,13 @@ DevMem& DevMem::operator=(DevMem&& o) noexcept {
     return *this;
 }
 
-namespace {
-
-using clk = std::chrono::steady_clock;
-
 void hipck(hipError_t e, const char* what) {
     if (e != hipSuccess) throw std::runtime_error(std::string("mpgmres: ") + what + ": " + hipGetErrorString(e));
 }
+
+namespace {
+
+using clk = std::chrono::steady_clock;
 
 // the driver's working types for a mode (gmres_perf_test.cpp:240-305)
 struct ModeTypes {
@@ -115,51 +115,15 @@ struct FusedEngine::Impl {
     // pipelined cycles: the next cycle's graph is launched before this
     // cycle's report is read; it starts by saving x, so a cycle launched past
     // a stop decision is undone by restoring x
-    bool pipeline = true;
     DevMem x_snap;
     hipEvent_t report_ev[2] = {nullptr, nullptr};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    bool use_graph = true;
-    bool fold = false;     // Givens step folded into the next SpMV launch
-    bool combine = false;  // last-arriver combines in the dots and CGS launches
-    bool cgs_partials = false;  // CGS update sums the dots partials in-launch
-    bool fuse_dots = false;     // ... from dots formed in the SpMV launch
-    bool fuse_dots_required = false;
-    int fuse_dots_k0 = 32;      // ... for the steps with k + 1 <= fuse_dots_k0
-    // the SpMV inside the dots' launch (mpg_arnoldi_step_dots; MPG_STEP_DOTS):
-    // 0 never, 1 wherever supported, 2 required, -1 the measured policy --
-    // the steps with step_dots_lo <= k + 1 <= step_dots_hi
-    int step_dots = 0;
-    int step_dots_lo = 1, step_dots_hi = 0;
-    int64_t dup_with_step = 0;  // time_phase_dup: CGS duplicates that re-ran that launch ahead of them
-    bool dup_step_only = false;  // ... duplicate that launch alone among the SpMV sites
-
-    // step k runs the SpMV and the dots in one launch
-    // (one GPU, plain CGS whose update sums the dots' partials itself, no ILU between the launches)
-    bool step_dots_engine_ok() const { return !(comm || sep_prec() || orth != MPG_ORTH_CGS || !cgs_partials || combine); }
-    bool step_dots_at(int k) const {
-        if (step_dots == 0) return false;
-        if (step_dots == 2) return true;  // (an unsupported step is then an error at its launch)
-        if (!step_dots_engine_ok()) return false;
-        if (step_dots < 0 && (k + 1 < step_dots_lo || k + 1 > step_dots_hi)) return false;
-        return mpg_arnoldi_step_dots_supported(arn, k) == MPG_OK;
+    CyclePolicy pol{};      // what decides the cycle's launches (resolve_policy)
+    std::vector<Op> cycle;  // plan_cycle(pol): the ops of one restart cycle
+    CapturedGraph graph;    // ... captured (ensure_graph)
+    void resolve_policy();
+    bool step_dots_at(int k) const {  // step k runs the SpMV inside the dots' launch (mpg_arnoldi_step_dots)
+        return std::any_of(cycle.begin(), cycle.end(), [k](const Op& o) { return o.kind == OpKind::StepDots && o.a == k; });
     }
-    int step_dots_steps() const {
-        int c = 0;
-        for (int k = 0; k < m; ++k) c += step_dots_at(k) && mpg_arnoldi_step_dots_supported(arn, k) == MPG_OK;
-        return c;
-    }
-    int timed = -1;                  // phase whose launches time_phase brackets with events
-    bool timed_inplace = false;      // ... the cycle's own SpMV launch, by its kernel events
-    bool timed_graph = false;        // ... external event nodes around it in a captured cycle
-    std::vector<hipEvent_t> marks;   // ... begin/end pairs
-    unsigned long long* stamps = nullptr;  // time_phase_stamps: wave stamp slots of each timed launch
-    int dup_phase = -1;   // time_phase_dup: phase whose site launches its kernel twice
-    int64_t dup_count = 0;  // ... extra launches captured
-    int64_t dup_with_dots = 0;  // ... of which re-ran the dots ahead of a CGS update
-    int64_t stamp_cap = 0, stamp_q = 0, stamp_max = 0;  // waves per launch, launches armed, launch slots
-    std::vector<int32_t> rowptr_host;
     mpg_ilu_t ilu = nullptr;  // ILU(0) factors (prec ilu / ilu_jacobi), applied between phase kernels
     // block Jacobi (prec bjacobi): bs x bs inverses of the nodes' diagonal blocks in the
     // preconditioner precision (mpg_bjacobi_setup_*), applied by a launch of
@@ -174,17 +138,11 @@ struct FusedEngine::Impl {
     // 54: 6 waves per SIMD instead of 8), point Jacobi 451
     // (profiles/r08_bjacobi/bjacobi_bench.json)
     bool bj_fused_step = false, bj_fused_prologue = false;
-    // a preconditioner applied between the phase kernels, not inside them
-    bool sep_prec() const { return ilu || bj_bs; }
-    bool sep_prec_step() const { return ilu || (bj_bs && !bj_fused_step); }
-    bool sep_prec_prologue() const { return ilu || (bj_bs && !bj_fused_prologue); }
     bool orthloss = false;    // LostOrthogonality: v_{k+1} stored each step, S / u below
     DevMem loss_S, loss_u;    // (m+1) x (m+1) and m+2 of T, zero-filled (IterUtil.hpp:185-191)
 
     ~Impl() {
         if (ilu) mpg_ilu_destroy(ilu);
-        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-        if (graph) (void)hipGraphDestroy(graph);
         if (arn) mpg_arnoldi_destroy(arn);
         if (csr) mpg_csr_destroy(csr);
         for (double* r : rep)
@@ -245,6 +203,89 @@ struct FusedEngine::Impl {
         return t == MPG_F64 ? s : (double)(float)s;
     }
 };
+
+// What decides the cycle's launches, read once: the environment, the ranks,
+// the preconditioner and what the workspace supports (mpg_cycle_policy, solve.h).
+void FusedEngine::Impl::resolve_policy() {
+    CyclePolicy& P = pol;
+    P.ranks = comm ? comm->size() : 0;
+    P.orth = orth;
+    P.m = m;
+    P.sep_prec = ilu || bj_bs;  // a preconditioner applied between the phase kernels, not inside them
+    P.sep_prec_step = ilu || (bj_bs && !bj_fused_step);
+    P.sep_prec_prologue = ilu || (bj_bs && !bj_fused_prologue);
+    P.partials_max_cols = mpg_arnoldi_partials_max_cols();
+    P.fold_max_m = mpg_arnoldi_fold_max_m();
+    for (int k = 0; k < std::min(m, MPG_CYCLE_POLICY_STEPS); ++k) {
+        P.step_dots_ok[k] = mpg_arnoldi_step_dots_supported(arn, k) == MPG_OK;
+        P.spmv_dots_ok[k] = mpg_arnoldi_spmv_dots_supported(arn, k) == MPG_OK;
+    }
+    // the first character of a setting; 0: unset or empty
+    auto env = [](const char* name) { const char* v = std::getenv(name); return v ? *v : '\0'; };
+    P.pipeline = env("MPG_PIPELINE") != '0';  // 0: read each cycle's report before the next launch
+    P.graph = env("MPG_NO_GRAPH") != '1' && (!comm || comm->capturable());
+    // Givens(k-1) is folded into SpMV(k) by default (MPG_FOLD_GIVENS=0: its
+    // own launch): every SpMV workgroup sums the 256 ||w||^2 partials of the
+    // 1024-thread CGS update itself (+1.9 us per SpMV, -4.6 us Givens launch
+    // and its boundary: 19.3k vs 18.7k it/s on BAND-10M). Experiments, off:
+    // MPG_COMBINE=1 (one GPU, CGS/CGSR) does last-arriver combines in the dots
+    // and CGS launches: 15.1k it/s (1024 tickets on one counter serialise).
+    // One GPU, by default (MPG_CGS_PARTIALS=0: off): every CGS workgroup sums
+    // the 256 dots partials per column itself (8 branch-free loads per lane,
+    // one latency) instead of the reduce launch: 21.6k vs 21.1k it/s on
+    // BAND-10M (tools/ab_bench.sh, 4 interleaved runs each).
+    P.combine = !comm && env("MPG_COMBINE") == '1' && orth != MPG_ORTH_MGS && m <= P.fold_max_m;
+    // (CGSR's first pass also emits the next dots: its in-launch form is the
+    // older runtime-count kernel, slower than reduce + update; on only with =1)
+    // (ranks: the dots' partials are all-reduced in place first, so the
+    // update still sums them itself -- no reduce launch per step)
+    P.cgs_partials = !P.combine && orth != MPG_ORTH_MGS &&
+                     (orth == MPG_ORTH_CGSR ? env("MPG_CGS_PARTIALS") == '1' : env("MPG_CGS_PARTIALS") != '0');
+    // MPG_FUSE_DOTS=1: the panel dots inside the SELL SpMV launch (SellDots)
+    // (=2: required -- an error where the storage does not support it; tests)
+    const char denv = env("MPG_FUSE_DOTS");
+    P.fuse_dots = P.cgs_partials && orth == MPG_ORTH_CGS && (denv == '1' || denv == '2');
+    P.fuse_dots_required = P.fuse_dots && denv == '2';
+    // MPG_FUSE_DOTS_K0=K: fuse only the steps with k + 1 <= K (the first
+    // steps, whose per-row basis loads are few; VERDICT r3 item 5's policy)
+    const char* kenv = std::getenv("MPG_FUSE_DOTS_K0");
+    P.fuse_dots_k0 = kenv && *kenv ? std::max(0, std::min(32, std::atoi(kenv))) : 32;
+    // MPG_STEP_DOTS: the SpMV inside the panel dots' launch (k_step_dots).
+    // 0 never, 1 wherever the launch is supported, 2 required (an unsupported
+    // step is an error; tests); unset: the steps with kStepDotsLo <= k + 1 <=
+    // kStepDotsHi, where the one launch measured faster than the two on
+    // BAND-10M in the fp32 accumulation class, the only one it is built for
+    // (profiles/r07_step_dots/). MPG_STEP_DOTS_LO / _HI move the range.
+    const char senv = env("MPG_STEP_DOTS");
+    P.step_dots = senv >= '0' && senv <= '2' ? senv - '0' : -1;
+    const char* lo = std::getenv("MPG_STEP_DOTS_LO");
+    const char* hi = std::getenv("MPG_STEP_DOTS_HI");
+    P.step_dots_lo = lo && *lo ? std::atoi(lo) : kStepDotsLo;
+    P.step_dots_hi = hi && *hi ? std::atoi(hi) : kStepDotsHi;
+    // MPG_FOLD_GIVENS: 0 never, 1 always (m permitting), unset: where it pays
+    // (mpg_arnoldi_fold_pays: up to ~4k SpMV workgroups)
+    const char fenv = env("MPG_FOLD_GIVENS");
+    bool fold_on = fenv ? fenv != '0' : mpg_arnoldi_fold_pays(arn) != 0;
+    if (comm && !fenv) {
+        // ranks of one solve must run the same collective sequence (a folding
+        // rank all-reduces the ||w||^2 partials with the halo, a non-folding
+        // one reduces + all-reduces one sum after it): every rank's row block
+        // and SELL layout differ, so the fold is taken only if it pays on
+        // EVERY rank (all-reduce max of "does not pay")
+        double* flag = scal.as<double>() + 6;
+        const double no = fold_on ? 0.0 : 1.0;
+        check(mpg_memcpy_h2d(ctx, flag, &no, sizeof no), "h2d", ctx);
+        comm->allreduce_max(flag, 1, stream());
+        double any_no = 0;
+        check(mpg_memcpy_d2h(ctx, &any_no, flag, sizeof any_no), "d2h", ctx);
+        fold_on = any_no == 0.0;
+    }
+    P.fold = !P.combine && fold_on && m <= P.fold_max_m;
+    if (int st = plan_cycle(P, cycle))
+        throw StatusError(st, "MPG_STEP_DOTS=2 / MPG_FUSE_DOTS=2: a step of the cycle cannot take the required SpMV + "
+                              "dots launch (one GPU, plain CGS with in-launch sums, no preconditioner launch -- ILU, "
+                              "block Jacobi -- between the SpMV and the dots, storage the launch supports)");
+}
 
 FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int n_ext, int n_front)
     : p_(new Impl) {
@@ -465,9 +506,6 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     for (double*& r : I.rep) hipck(hipHostMalloc((void**)&r, (size_t)I.report_len * sizeof(double), 0), "hipHostMalloc");
     I.report_host = I.rep[0];
     for (hipEvent_t& e : I.report_ev) hipck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "event");
-    const char* qenv = std::getenv("MPG_PIPELINE");  // 0: read each cycle's report before the next launch
-    I.pipeline = !(qenv && *qenv == '0');
-    if (I.pipeline) I.x_snap = DevMem(ctx, I.x.bytes);
 
     // convergence strategy (gmres_perf_test.cpp:185-196)
     const size_t mm = (size_t)a.rlen, mr = (size_t)a.max_restarts;
@@ -483,69 +521,8 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     conv_->total_iters = 0;
     breakdown.stop = a.stop_on_breakdown != 0;
 
-    const char* env = std::getenv("MPG_NO_GRAPH");
-    I.use_graph = !(env && *env == '1') && (!comm || comm->capturable());
-    // Givens(k-1) is folded into SpMV(k) by default (MPG_FOLD_GIVENS=0: its
-    // own launch): every SpMV workgroup sums the 256 ||w||^2 partials of the
-    // 1024-thread CGS update itself (+1.9 us per SpMV, -4.6 us Givens launch
-    // and its boundary: 19.3k vs 18.7k it/s on BAND-10M). Experiments, off:
-    // MPG_COMBINE=1 (one GPU, CGS/CGSR) does last-arriver combines in the dots
-    // and CGS launches: 15.1k it/s (1024 tickets on one counter serialise).
-    // One GPU, by default (MPG_CGS_PARTIALS=0: off): every CGS workgroup sums
-    // the 256 dots partials per column itself (8 branch-free loads per lane,
-    // one latency) instead of the reduce launch: 21.6k vs 21.1k it/s on
-    // BAND-10M (tools/ab_bench.sh, 4 interleaved runs each).
-    const char* cenv = std::getenv("MPG_COMBINE");
-    I.combine = !comm && cenv && *cenv == '1' && I.orth != MPG_ORTH_MGS && I.m <= mpg_arnoldi_fold_max_m();
-    const char* penv = std::getenv("MPG_CGS_PARTIALS");
-    // (CGSR's first pass also emits the next dots: its in-launch form is the
-    // older runtime-count kernel, slower than reduce + update; on only with =1)
-    // (ranks: the dots' partials are all-reduced in place first, so the
-    // update still sums them itself -- no reduce launch per step)
-    I.cgs_partials = !I.combine && I.orth != MPG_ORTH_MGS &&
-                     (I.orth == MPG_ORTH_CGSR ? (penv && *penv == '1') : !(penv && *penv == '0'));
-    // MPG_FUSE_DOTS=1: the panel dots inside the SELL SpMV launch (SellDots)
-    const char* denv = std::getenv("MPG_FUSE_DOTS");
-    // (=2: required -- an error where the storage does not support it; tests)
-    I.fuse_dots = I.cgs_partials && I.orth == MPG_ORTH_CGS && denv && (*denv == '1' || *denv == '2');
-    I.fuse_dots_required = I.fuse_dots && *denv == '2';
-    // MPG_FUSE_DOTS_K0=K: fuse only the steps with k + 1 <= K (the first
-    // steps, whose per-row basis loads are few; VERDICT r3 item 5's policy)
-    const char* kenv = std::getenv("MPG_FUSE_DOTS_K0");
-    I.fuse_dots_k0 = kenv && *kenv ? std::max(0, std::min(32, std::atoi(kenv))) : 32;
-    // MPG_STEP_DOTS: the SpMV inside the panel dots' launch (k_step_dots).
-    // 0 never, 1 wherever the launch is supported, 2 required (an unsupported
-    // step is an error; tests); unset: the steps with kStepDotsLo <= k + 1 <=
-    // kStepDotsHi, where the one launch measured faster than the two on
-    // BAND-10M in the fp32 accumulation class, the only one it is built for
-    // (profiles/r07_step_dots/). MPG_STEP_DOTS_LO / _HI move the range.
-    {
-        const char* senv = std::getenv("MPG_STEP_DOTS");
-        I.step_dots = senv && *senv >= '0' && *senv <= '2' ? *senv - '0' : -1;
-        const char* lo = std::getenv("MPG_STEP_DOTS_LO");
-        const char* hi = std::getenv("MPG_STEP_DOTS_HI");
-        I.step_dots_lo = lo && *lo ? std::atoi(lo) : kStepDotsLo;
-        I.step_dots_hi = hi && *hi ? std::atoi(hi) : kStepDotsHi;
-    }
-    // MPG_FOLD_GIVENS: 0 never, 1 always (m permitting), unset: where it pays
-    // (mpg_arnoldi_fold_pays: up to ~4k SpMV workgroups)
-    const char* fenv = std::getenv("MPG_FOLD_GIVENS");
-    bool fold_on = fenv && *fenv ? *fenv != '0' : mpg_arnoldi_fold_pays(I.arn) != 0;
-    if (comm && !(fenv && *fenv)) {
-        // ranks of one solve must run the same collective sequence (a folding
-        // rank all-reduces the ||w||^2 partials with the halo, a non-folding
-        // one reduces + all-reduces one sum after it): every rank's row block
-        // and SELL layout differ, so the fold is taken only if it pays on
-        // EVERY rank (all-reduce max of "does not pay")
-        double* flag = I.scal.as<double>() + 6;
-        const double no = fold_on ? 0.0 : 1.0;
-        check(mpg_memcpy_h2d(ctx, flag, &no, sizeof no), "h2d", ctx);
-        comm->allreduce_max(flag, 1, I.stream());
-        double any_no = 0;
-        check(mpg_memcpy_d2h(ctx, &any_no, flag, sizeof any_no), "d2h", ctx);
-        fold_on = any_no == 0.0;
-    }
-    I.fold = !I.combine && fold_on && I.m <= mpg_arnoldi_fold_max_m();
+    I.resolve_policy();
+    if (I.pol.pipeline) I.x_snap = DevMem(ctx, I.x.bytes);
     check(mpg_ctx_sync(ctx), "sync", ctx);
     setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
     prologue();
@@ -557,198 +534,66 @@ FusedEngine::~FusedEngine() = default;
 
 void FusedEngine::sync() { check(mpg_ctx_sync(p_->ctx), "sync", p_->ctx); }
 
+// One op of the cycle's list (cycle_plan.hpp): the only place the cycle's
+// launches and collectives are made.
+void FusedEngine::issue(const Op& o) {
+    Impl& I = *p_;
+    const mpg_arnoldi_t A = I.arn;
+    const hipStream_t s = I.stream();
+    switch (o.kind) {
+        case OpKind::XSnapshot:  // the cycle may run past a stop decision: keep the x it started from
+            return hipck(hipMemcpyAsync(I.x_snap.p, I.x.p, I.x.bytes, hipMemcpyDeviceToDevice, s), "x snapshot");
+        case OpKind::Halo:
+            if (o.a < 0) return I.comm->halo(I.xp, (int)dsize(I.ty.X), s);
+            return I.comm->halo(mpg_arnoldi_wprev_dev(A, o.a), mpg_arnoldi_vec_bytes(A), s);
+        case OpKind::AllreducePartialsHalo:
+            return I.comm->allreduce_sum_and_halo(mpg_arnoldi_partials_dev(A), mpg_arnoldi_partials_count(A),
+                                                  mpg_arnoldi_wprev_dev(A, o.a), mpg_arnoldi_vec_bytes(A), s);
+        case OpKind::Spmv: return check(mpg_arnoldi_spmv(A, o.a), "spmv", I.ctx);
+        case OpKind::GivensSpmv: return check(mpg_arnoldi_givens_partials_spmv(A, o.a), "givens+spmv", I.ctx);
+        case OpKind::SpmvDots: return check(mpg_arnoldi_spmv_dots(A, o.a, o.b), "spmv+dots", I.ctx);
+        case OpKind::StepDots: return check(mpg_arnoldi_step_dots(A, o.a, o.b), "spmv+dots", I.ctx);
+        case OpKind::ApplyPrec: return I.apply_ilu(mpg_arnoldi_wprev_dev(A, o.a));
+        case OpKind::Dots: return check(mpg_arnoldi_dots(A, o.a), "dots", I.ctx);
+        case OpKind::DotsSums: return check(mpg_arnoldi_dots_sums(A, o.a), "dots+sums", I.ctx);
+        case OpKind::AllreducePartials:
+            // the last launch's partials, [column][workgroup] (uniform workgroup
+            // counts on every rank: mpg_arnoldi_uniform_groups), summed in place
+            // (bit-identical on every rank), for a consumer that sums them itself
+            return I.comm->allreduce_sum(mpg_arnoldi_partials_dev(A), (int64_t)o.a * mpg_arnoldi_partials_count(A), s);
+        case OpKind::Reduce: return check(mpg_arnoldi_reduce(A, o.a), "reduce", I.ctx);
+        case OpKind::AllreduceSums: return I.comm->allreduce_sum(mpg_arnoldi_sums_dev(A), o.a, s);
+        case OpKind::CgsPartials: return check(mpg_arnoldi_cgs_partials(A, o.a), "cgs", I.ctx);
+        case OpKind::Cgs: return check(mpg_arnoldi_cgs(A, o.a, o.b), "cgs", I.ctx);
+        case OpKind::CgsGivens: return check(mpg_arnoldi_cgs_givens(A, o.a, o.b), "cgs+givens", I.ctx);
+        case OpKind::CgsrWidePass: return check(mpg_arnoldi_cgsr_wide_pass(A, o.a, o.b), "cgsr", I.ctx);
+        case OpKind::MgsPartials: return check(mpg_arnoldi_mgs_partials(A, o.a, o.b), "mgs", I.ctx);
+        case OpKind::Givens: return check(mpg_arnoldi_givens(A, o.a), "givens", I.ctx);
+        case OpKind::GivensPartials: return check(mpg_arnoldi_givens_partials(A, o.a), "givens", I.ctx);
+        case OpKind::Update: return check(mpg_arnoldi_update(A, o.a), "update", I.ctx);
+        case OpKind::Prologue: return check(mpg_arnoldi_prologue(A), "prologue", I.ctx);
+        case OpKind::PrologueWnorm: return check(mpg_arnoldi_prologue_wnorm(A), "prologue wnorm", I.ctx);
+        case OpKind::PrologueFinish: return check(mpg_arnoldi_prologue_finish(A), "prologue_finish", I.ctx);
+        case OpKind::PrologueFinishPartials:
+            return check(mpg_arnoldi_prologue_finish_partials(A), "prologue_finish", I.ctx);
+    }
+}
+
+void FusedEngine::issue(const std::vector<Op>& ops) {
+    for (const Op& o : ops) issue(o);
+}
+
 void FusedEngine::prologue() {
-    Impl& I = *p_;
-    if (I.comm) I.comm->halo(I.xp, (int)dsize(I.ty.X), I.stream());
-    timed(1, [&] { check(mpg_arnoldi_prologue(I.arn), "prologue", I.ctx); });
-    check(mpg_arnoldi_prologue(I.arn), "prologue", I.ctx);
-    if (I.sep_prec()) {  // w = M(T(r)) outside the kernel, then ||w||^2 again
-        // (block Jacobi inside the prologue: only the norm, in the order the
-        // separate form sums it, so both forms give one beta)
-        if (I.sep_prec_prologue()) I.apply_ilu(mpg_arnoldi_wprev_dev(I.arn, 0));
-        check(mpg_arnoldi_prologue_wnorm(I.arn), "prologue wnorm", I.ctx);
-    }
-    if (!I.comm) {  // the 3 column sums inside the finish launch (same bits)
-        check(mpg_arnoldi_prologue_finish_partials(I.arn), "prologue_finish", I.ctx);
-        return;
-    }
-    check(mpg_arnoldi_reduce(I.arn, 3), "reduce", I.ctx);
-    I.comm->allreduce_sum(mpg_arnoldi_sums_dev(I.arn), 3, I.stream());
-    check(mpg_arnoldi_prologue_finish(I.arn), "prologue_finish", I.ctx);
+    std::vector<Op> ops;
+    plan_prologue(p_->pol, ops);
+    issue(ops);
 }
 
-// ranks: sum the last kernel's per-workgroup partials across ranks in place
-// (bit-identical on every rank), for a consumer that sums them itself
-void FusedEngine::allreduce_partials(int ncols) {
-    Impl& I = *p_;
-    // the last launch's partials, [column][workgroup] (uniform workgroup
-    // counts on every rank: mpg_arnoldi_uniform_groups), summed in place
-    I.comm->allreduce_sum(mpg_arnoldi_partials_dev(I.arn), (int64_t)ncols * mpg_arnoldi_partials_count(I.arn),
-                          I.stream());
-}
-
-void FusedEngine::reduce(int nc) {
-    Impl& I = *p_;
-    check(mpg_arnoldi_reduce(I.arn, nc), "reduce", I.ctx);
-    if (I.comm) I.comm->allreduce_sum(mpg_arnoldi_sums_dev(I.arn), nc, I.stream());
-}
-
-// ||w||^2: one GPU folds the partial sums into the Givens kernel; ranks of a
-// partitioned solve reduce + all-reduce first
-void FusedEngine::givens(int k) {
-    Impl& I = *p_;
-    if (I.comm) {
-        reduce(1);
-        check(mpg_arnoldi_givens(I.arn, k), "givens", I.ctx);
-    } else {
-        check(mpg_arnoldi_givens_partials(I.arn, k), "givens", I.ctx);
-    }
-}
-
-// Arnoldi step k. fold: the Givens step k-1 rides in this step's SpMV
-// launch (k >= 1) and step k's own Givens is left to step k+1 / the caller.
+// Arnoldi step k on its own (the stepwise strategies). fold as in plan_step.
 void FusedEngine::step(int k, bool fold) {
-    Impl& I = *p_;
-    // SpMV and panel dots in one launch (one GPU, CGS with in-launch sums)
-    if (I.fuse_dots && !I.comm && !I.sep_prec() && I.orth == MPG_ORTH_CGS && I.cgs_partials && !I.combine &&
-        k + 1 <= I.fuse_dots_k0) {
-        timed(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
-        const int st = mpg_arnoldi_spmv_dots(I.arn, k, fold && k > 0 ? 2 : 0);
-        timed_end(0);
-        if (st == MPG_OK) {
-            check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx);
-            if (!fold) givens(k);
-            return;
-        }
-        if (st != MPG_ERR_UNSUPPORTED || I.fuse_dots_required) check(st, "spmv+dots", I.ctx);
-        I.fuse_dots = false;  // not available for this storage: the separate launches below
-    }
-    // the SpMV inside the panel dots' launch, then straight to the update
-    // that sums the dots' partials itself (MPG_STEP_DOTS; same bits)
-    if (I.step_dots_at(k)) {
-        const int f = fold && k > 0 ? 2 : 0;
-        if (!I.step_dots_engine_ok())
-            throw StatusError(MPG_ERR_UNSUPPORTED, "MPG_STEP_DOTS=2: the SpMV + dots launch needs one GPU and plain CGS "
-                                                   "with in-launch sums, without a preconditioner launch (ILU, "
-                                                   "block Jacobi) between the SpMV and the dots");
-        timed(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
-        const int st = mpg_arnoldi_step_dots(I.arn, k, f);
-        if (st == MPG_OK) {
-            dup(0, [&] { check(mpg_arnoldi_step_dots(I.arn, k, f), "spmv+dots", I.ctx); });
-            timed_end(0);
-            timed(2, [&] { check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx); });
-            check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx);
-            // (the update's own partials replaced nothing the launch before it
-            // reads, but its duplicate needs w = A v_k and the dots again: the
-            // one launch is re-run ahead, and time_phase_dup takes its share out)
-            dup(2, [&] {
-                check(mpg_arnoldi_step_dots(I.arn, k, f), "spmv+dots", I.ctx);
-                check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx);
-                ++I.dup_with_step;
-            });
-            timed_end(2);
-            if (!fold) givens(k);
-            return;
-        }
-        timed_end(0);
-        check(st, "spmv+dots", I.ctx);  // (step_dots_at asked: unsupported here means MPG_STEP_DOTS=2)
-    }
-    if (I.dup_step_only && I.dup_phase == 0) {
-        // (time_phase_dup's own correction run: only the launches above are doubled)
-        const int keep = I.dup_phase;
-        I.dup_phase = -1;
-        step(k, fold);
-        I.dup_phase = keep;
-        return;
-    }
-    if (fold && k > 0) {
-        if (I.comm)  // the ||w||^2 partials' all-reduce and the w_prev halo in one RCCL group
-            I.comm->allreduce_sum_and_halo(mpg_arnoldi_partials_dev(I.arn), mpg_arnoldi_partials_count(I.arn),
-                                           mpg_arnoldi_wprev_dev(I.arn, k), mpg_arnoldi_vec_bytes(I.arn),
-                                           I.stream());
-        timed(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
-        check(mpg_arnoldi_givens_partials_spmv(I.arn, k), "givens+spmv", I.ctx);
-        dup(0, [&] { check(mpg_arnoldi_givens_partials_spmv(I.arn, k), "givens+spmv", I.ctx); });
-        timed_end(0);
-    } else {
-        if (I.comm) I.comm->halo(mpg_arnoldi_wprev_dev(I.arn, k), mpg_arnoldi_vec_bytes(I.arn), I.stream());
-        timed(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
-        check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx);
-        dup(0, [&] { check(mpg_arnoldi_spmv(I.arn, k), "spmv", I.ctx); });
-        timed_end(0);
-    }
-    if (I.sep_prec_step()) I.apply_ilu(mpg_arnoldi_wprev_dev(I.arn, k + 1));  // w = M(A v_k)
-    if (I.orth == MPG_ORTH_MGS) {
-        check(mpg_arnoldi_dots(I.arn, k), "dots", I.ctx);
-        if (!I.comm) {  // one GPU: each update sums the previous launch's partials itself
-            for (int j = 0; j <= k; ++j) check(mpg_arnoldi_mgs_partials(I.arn, k, j), "mgs", I.ctx);
-        } else {  // ranks: all-reduce the 256 partials in place, then the same in-launch sums
-            for (int j = 0; j <= k; ++j) {
-                allreduce_partials(1);
-                check(mpg_arnoldi_mgs_partials(I.arn, k, j), "mgs", I.ctx);
-            }
-        }
-    } else {
-        // MPG_CGS_PARTIALS=1 (one GPU, k+1 <= 32): the CGS update sums the dots
-        // partials itself; MPG_COMBINE=1: the dots' last workgroup writes the
-        // sums and the last CGS pass's last workgroup runs the Givens step
-        // (one GPU, plain CGS: up to 128 columns -- GMRES(100) -- the wide
-        // update sums the one-launch panel dots' partials itself)
-        const bool small = k + 1 <= 32 || (!I.comm && I.orth == MPG_ORTH_CGS && k + 1 <= mpg_arnoldi_partials_max_cols());
-        if (!I.comm && !I.combine && I.orth == MPG_ORTH_CGSR && k + 1 > 32 &&
-            k + 1 <= mpg_arnoldi_partials_max_cols()) {
-            // CGSR at GMRES(100): dots, pass 0, dots again on the updated w, pass 1
-            for (int pass = 0; pass < 2; ++pass) {
-                check(mpg_arnoldi_dots(I.arn, k), "dots", I.ctx);
-                check(mpg_arnoldi_cgsr_wide_pass(I.arn, k, pass), "cgsr", I.ctx);
-            }
-            if (!fold) givens(k);
-            return;
-        }
-        const int last_pass = I.orth == MPG_ORTH_CGSR ? 1 : 0;
-        bool pass0_done = false;
-        if (I.combine && k + 1 <= 32) {
-            check(mpg_arnoldi_dots_sums(I.arn, k), "dots+sums", I.ctx);
-        } else {
-            timed(3, [&] { check(mpg_arnoldi_dots(I.arn, k), "dots", I.ctx); });
-            check(mpg_arnoldi_dots(I.arn, k), "dots", I.ctx);
-            dup(3, [&] { check(mpg_arnoldi_dots(I.arn, k), "dots", I.ctx); });
-            timed_end(3);
-            if (I.cgs_partials && small) {
-                if (I.comm) allreduce_partials(k + 1);
-                timed(2, [&] { check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx); });
-                check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx);
-                // (the in-launch sums read the dots' partials, which the first
-                // update's own partials replaced: the duplicate re-runs the
-                // dots first, and time_phase_dup takes their share back out)
-                dup(2, [&] {
-                    check(mpg_arnoldi_dots(I.arn, k), "dots", I.ctx);
-                    check(mpg_arnoldi_cgs_partials(I.arn, k), "cgs", I.ctx);
-                    ++I.dup_with_dots;
-                });
-                timed_end(2);
-                pass0_done = true;
-            } else {
-                reduce(k + 1);
-            }
-        }
-        if (last_pass == 1) {
-            if (!pass0_done) check(mpg_arnoldi_cgs(I.arn, k, 0), "cgs", I.ctx);
-            reduce(k + 1);
-        } else if (pass0_done) {
-            if (!fold) givens(k);
-            return;
-        }
-        if (I.combine) {
-            check(mpg_arnoldi_cgs_givens(I.arn, k, last_pass), "cgs+givens", I.ctx);
-            return;
-        }
-        timed(2, [&] { check(mpg_arnoldi_cgs(I.arn, k, last_pass), "cgs", I.ctx); });
-        check(mpg_arnoldi_cgs(I.arn, k, last_pass), "cgs", I.ctx);
-        dup(2, [&] { check(mpg_arnoldi_cgs(I.arn, k, last_pass), "cgs", I.ctx); });
-        timed_end(2);
-    }
-    if (!fold) givens(k);
+    std::vector<Op> ops;
+    check(plan_step(p_->pol, k, fold, ops), "step plan", p_->ctx);
+    issue(ops);
 }
 
 // v_{k+1} = T(w * (1/h_{k+1,k})) into V(:,k+1) right after step k, as the
@@ -797,7 +642,7 @@ double FusedEngine::orth_loss_step(size_t kk) {
     return (double)d;
 }
 
-void FusedEngine::update(int k) { check(mpg_arnoldi_update(p_->arn, k), "update", p_->ctx); }
+void FusedEngine::update(int k) { issue(Op{OpKind::Update, -1, false, 0, k, 0}); }
 
 void FusedEngine::read_report(int count) {
     Impl& I = *p_;
@@ -868,18 +713,6 @@ void FusedEngine::wait_event(hipEvent_t ev, int64_t cycle, const char* what) {
     }
 }
 
-// steps 0..m-1, solution update with k = m, next residual prologue
-void FusedEngine::cycle_program() {
-    Impl& I = *p_;
-    if (I.pipeline)  // the cycle may run past a stop decision: keep the x it started from
-        hipck(hipMemcpyAsync(I.x_snap.p, I.x.p, I.x.bytes, hipMemcpyDeviceToDevice, I.stream()), "x snapshot");
-    const bool fold = I.fold;
-    for (int k = 0; k < I.m; ++k) step(k, fold);
-    if (fold) givens(I.m - 1);
-    update(I.m);
-    prologue();
-}
-
 // check_initial on the report of the last prologue (gmres.cpp:171-190)
 bool FusedEngine::check_start(int64_t i) {
     Impl& I = *p_;
@@ -913,23 +746,12 @@ bool FusedEngine::check_start(int64_t i) {
 // that cannot be captured) fall back to eager launches for good
 void FusedEngine::ensure_graph() {
     Impl& I = *p_;
-    if (!I.use_graph || I.graph_exec) return;
-    hipck(hipStreamBeginCapture(I.stream(), hipStreamCaptureModeThreadLocal), "begin capture");
-    bool ok = true;
+    if (!I.pol.graph || I.graph.exec) return;
     try {
-        cycle_program();
+        I.graph = CapturedGraph(I.stream(), [this] { issue(p_->cycle); });
     } catch (const std::exception& ex) {
-        ok = false;
         std::fprintf(stderr, "mpgmres: cycle capture failed (%s); running eagerly\n", ex.what());
-    }
-    hipGraph_t g = nullptr;
-    const hipError_t ec = hipStreamEndCapture(I.stream(), &g);
-    if (ok && ec == hipSuccess && hipGraphInstantiate(&I.graph_exec, g, nullptr, nullptr, 0) == hipSuccess) {
-        I.graph = g;
-    } else {
-        if (g) (void)hipGraphDestroy(g);
-        (void)hipGetLastError();
-        I.use_graph = false;
+        I.pol.graph = 0;
     }
 }
 
@@ -962,7 +784,7 @@ int FusedEngine::run_pipelined(int max_cycles, bool& done) {
     if (max_cycles <= 0) return 0;
     // one replay of the captured cycle, then its report into rep[p], marked by report_ev[p]
     auto launch = [&](int p) {
-        hipck(hipGraphLaunch(I.graph_exec, I.stream()), "graph launch");
+        hipck(hipGraphLaunch(I.graph.exec, I.stream()), "graph launch");
         hipck(hipMemcpyAsync(I.rep[p], mpg_arnoldi_report_dev(I.arn), (size_t)I.report_len * sizeof(double),
                              hipMemcpyDeviceToHost, I.stream()),
               "report d2h");
@@ -1015,7 +837,7 @@ int FusedEngine::run_cycles(int max_cycles, bool& done) {
     int ran = 0;
     const bool stepwise = conv_->needs_arnoldi_residual();
     if (!stepwise) ensure_graph();
-    if (!stepwise && I.use_graph && I.pipeline) return run_pipelined(max_cycles, done);
+    if (!stepwise && I.pol.graph && I.pol.pipeline) return run_pipelined(max_cycles, done);
     for (; ran < max_cycles; ++ran) {
         const int64_t i = (int64_t)cycles.size();
         if (check_start(i)) {
@@ -1023,8 +845,8 @@ int FusedEngine::run_cycles(int max_cycles, bool& done) {
             return ran;
         }
         if (!stepwise) {
-            if (I.use_graph) hipck(hipGraphLaunch(I.graph_exec, I.stream()), "graph launch");
-            else cycle_program();
+            if (I.pol.graph) hipck(hipGraphLaunch(I.graph.exec, I.stream()), "graph launch");
+            else issue(I.cycle);  // steps 0..m-1, solution update with k = m, next residual prologue
             read_report(I.report_len);
             if (I.ilu) check_ilu_fault(I.ilu);
             record_steps(i);
@@ -1141,350 +963,14 @@ double FusedEngine::phase_bytes(int which) const {
 
 mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
-bool FusedEngine::givens_folded() const { return p_->fold; }
 int FusedEngine::prec_fused() const { return p_->bj_bs ? (p_->bj_fused_step ? 1 : 0) : -1; }
-int FusedEngine::step_dots_steps() const { return p_->step_dots_steps(); }
-int FusedEngine::step_dots_status(int k) const { return mpg_arnoldi_step_dots_supported(p_->arn, k); }
-
-// Device-event time of one phase kernel in its place in the cycle: `reps`
-// restart cycles run eagerly in cycle order, and at every launch of phase
-// `which` the plain form of that kernel is first replayed kTimedReplays
-// times back to back between one event pair (amortising the dispatch
-// latency an event pair around a single launch would include), then the
-// cycle's own launch follows. Replays of the non-idempotent CGS update leave
-// the engine's state meaningless: time_phase is for measurement only.
-constexpr int kTimedReplays = 10;
-
-double FusedEngine::time_phase(int which, int reps, bool inplace, std::vector<double>* per_launch) {
-    measured = true;
-    Impl& I = *p_;
-    if (inplace && which != 0) throw std::invalid_argument("in-place timing covers the Arnoldi SpMV only");
-    I.timed = which;
-    I.timed_inplace = inplace;
-    I.marks.clear();
-    for (int r = 0; r < reps; ++r) cycle_program();
-    I.timed = -1;
-    I.timed_inplace = false;
-    hipck(hipStreamSynchronize(I.stream()), "sync");
-    float total_ms = 0;
-    const size_t pairs = I.marks.size() / 2;
-    for (size_t q = 0; q < pairs; ++q) {
-        float ms = 0;
-        hipck(hipEventElapsedTime(&ms, I.marks[2 * q], I.marks[2 * q + 1]), "elapsed");
-        total_ms += ms;
-        if (per_launch) per_launch->push_back(inplace ? ms : ms / kTimedReplays);
-    }
-    for (hipEvent_t e : I.marks) (void)hipEventDestroy(e);
-    I.marks.clear();
-    return pairs ? total_ms / (pairs * (inplace ? 1 : kTimedReplays)) : 0.0;
+int FusedEngine::step_dots_steps() const {
+    return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::StepDots; });
 }
-
-// replay mode: kTimedReplays plain launches between one event pair ahead of
-// the site's own launch; in-place mode (SpMV): arm the kernel events that
-// the site's own launch records (mpg_arnoldi_time_next_spmv)
-// An event-record node spliced into the capture in progress on `st`: the
-// node depends on the capture's current tail and becomes the new tail. Same
-// place in the graph as hipEventRecordWithFlags(hipEventRecordExternal),
-// which the HIP runtime bundled with PyTorch (ROCm 7.0) rejects inside a
-// capture ("invalid argument").
-static void capture_event_record(hipStream_t st, hipEvent_t ev) {
-    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
-    unsigned long long id = 0;
-    hipGraph_t graph = nullptr;
-    const hipGraphNode_t* deps = nullptr;
-    size_t ndeps = 0;
-    hipck(hipStreamGetCaptureInfo_v2(st, &status, &id, &graph, &deps, &ndeps), "capture info");
-    if (status != hipStreamCaptureStatusActive || !graph) throw StatusError(MPG_ERR_HIP, "timing mark outside a capture");
-    hipGraphNode_t node = nullptr;
-    hipck(hipGraphAddEventRecordNode(&node, graph, deps, ndeps, ev), "event record node");
-    hipck(hipStreamUpdateCaptureDependencies(st, &node, 1, hipStreamSetCaptureDependencies), "capture tail");
-}
-
-// time_phase_dup: the site's own launch once more, right behind it (the same
-// kernel, arguments and queue position)
-template <class F>
-void FusedEngine::dup(int phase, F&& launch) {
-    Impl& I = *p_;
-    if (I.dup_phase != phase) return;
-    launch();
-    ++I.dup_count;
-}
-
-template <class F>
-void FusedEngine::timed(int phase, F&& launch) {
-    Impl& I = *p_;
-    if (I.timed != phase) return;
-    if (I.stamps) {
-        // wave stamps of the site's own launch (disarmed again by timed_end,
-        // so a site that launches another form stores nothing)
-        if (I.stamp_q < I.stamp_max)
-            check(mpg_arnoldi_stamp_next(I.arn, I.stamps + 2 * I.stamp_cap * I.stamp_q++, I.stamp_cap), "stamp",
-                  I.ctx);
-        return;
-    }
-    if (I.timed_graph) {
-        // an external event node ahead of the site's own launch (its pair
-        // follows the launch: timed_end)
-        hipEvent_t e0;
-        hipck(hipEventCreate(&e0), "event");
-        I.marks.push_back(e0);
-        capture_event_record(I.stream(), e0);
-        return;
-    }
-    hipEvent_t e[2];
-    for (auto& x : e) hipck(hipEventCreate(&x), "event");
-    if (I.timed_inplace) {
-        check(mpg_arnoldi_time_next_spmv(I.arn, e[0], e[1]), "time spmv", I.ctx);
-    } else {
-        hipck(hipEventRecord(e[0], I.stream()), "record");
-        for (int r = 0; r < kTimedReplays; ++r) launch();
-        hipck(hipEventRecord(e[1], I.stream()), "record");
-    }
-    I.marks.push_back(e[0]);
-    I.marks.push_back(e[1]);
-}
-
-void FusedEngine::timed_end(int phase) {
-    Impl& I = *p_;
-    if (I.timed != phase) return;
-    if (I.stamps) {
-        check(mpg_arnoldi_stamp_next(I.arn, nullptr, 0), "stamp", I.ctx);
-        return;
-    }
-    if (!I.timed_graph) return;
-    hipEvent_t e1;
-    hipck(hipEventCreate(&e1), "event");
-    I.marks.push_back(e1);
-    capture_event_record(I.stream(), e1);
-}
-
-// A phase kernel timed inside graph replays of the cycle (which: 0 the
-// Arnoldi SpMV, 2 the CGS update, 3 the panel dots): the cycle is captured
-// once more with an external event node on each side of every launch of
-// that phase, and that graph is replayed `reps` times (each replay
-// re-records the events; they are read after it). Measurement only, like
-// time_phase: the replays run without the host's restart checks.
-double FusedEngine::time_phase_graph(int which, int reps, std::vector<double>* per_launch) {
-    measured = true;
-    Impl& I = *p_;
-    if (!I.use_graph) throw StatusError(MPG_ERR_UNSUPPORTED, "the cycle is not captured (MPG_NO_GRAPH / eager ranks)");
-    if (which != 0 && which != 2 && which != 3) throw std::invalid_argument("phase: 0 spmv, 2 cgs update, 3 dots");
-    I.timed = which;
-    I.timed_graph = true;
-    I.marks.clear();
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    double total = 0;
-    size_t count = 0;
-    auto cleanup = [&] {
-        I.timed = -1;
-        I.timed_graph = false;
-        if (ge) (void)hipGraphExecDestroy(ge);
-        if (g) (void)hipGraphDestroy(g);
-        for (hipEvent_t e : I.marks) (void)hipEventDestroy(e);
-        I.marks.clear();
-    };
-    try {
-        hipck(hipStreamBeginCapture(I.stream(), hipStreamCaptureModeThreadLocal), "begin capture");
-        try {
-            cycle_program();
-        } catch (...) {
-            (void)hipStreamEndCapture(I.stream(), &g);
-            throw;
-        }
-        hipck(hipStreamEndCapture(I.stream(), &g), "end capture");
-        hipck(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0), "instantiate");
-        const size_t pairs = I.marks.size() / 2;
-        for (int r = 0; r < reps; ++r) {
-            hipck(hipGraphLaunch(ge, I.stream()), "graph launch");
-            hipck(hipStreamSynchronize(I.stream()), "sync");
-            for (size_t q = 0; q < pairs; ++q) {
-                float ms = 0;
-                hipck(hipEventElapsedTime(&ms, I.marks[2 * q], I.marks[2 * q + 1]), "elapsed");
-                total += ms;
-                ++count;
-                if (per_launch) per_launch->push_back(ms);
-            }
-        }
-    } catch (...) {
-        cleanup();
-        (void)hipGetLastError();
-        throw;
-    }
-    cleanup();
-    return count ? total / count : 0.0;
-}
-
-// A phase kernel's own duration inside graph replays of the cycle (which: 0
-// the Arnoldi SpMV, 2 the one-panel CGS update, 3 the one-panel dots): the
-// cycle is captured once more (after a memset node clearing the slots) with
-// every launch of that phase storing its waves' wall-clock stamps
-// (mpg_arnoldi_stamp_next); a launch lasts max(end) - min(start) over its
-// waves -- the kernel alone, with no event packet in the queue around it.
-// Launches of another form at the phase's site (the panel kernels past 32
-// columns) store nothing and are skipped. Measurement only, like
-// time_phase_graph.
-double FusedEngine::time_phase_stamps(int which, int reps, std::vector<double>* per_launch) {
-    measured = true;
-    Impl& I = *p_;
-    if (!I.use_graph) throw StatusError(MPG_ERR_UNSUPPORTED, "the cycle is not captured (MPG_NO_GRAPH / eager ranks)");
-    if (which != 0 && which != 2 && which != 3) throw std::invalid_argument("phase: 0 spmv, 2 cgs update, 3 dots");
-    const int64_t cap = mpg_arnoldi_stamp_waves(I.arn);
-    if (cap < 1) throw StatusError(MPG_ERR_HIP, "no SpMV waves");
-    const int64_t slots = (int64_t)(I.m + 2);
-    const size_t bytes = (size_t)(2 * cap * slots) * sizeof(unsigned long long);
-    DevMem buf(I.ctx, bytes);
-    int dev = 0, khz = 0;
-    hipck(hipGetDevice(&dev), "device");
-    hipck(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev), "wall clock rate");
-    if (khz <= 0) throw StatusError(MPG_ERR_HIP, "no wall clock rate");
-    std::vector<unsigned long long> host(bytes / sizeof(unsigned long long));
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    double total = 0;
-    size_t count = 0;
-    I.timed = which;
-    I.stamps = buf.as<unsigned long long>();
-    I.stamp_cap = cap;
-    I.stamp_q = 0;
-    I.stamp_max = slots;
-    auto cleanup = [&] {
-        I.timed = -1;
-        I.stamps = nullptr;
-        I.stamp_q = I.stamp_max = 0;
-        if (ge) (void)hipGraphExecDestroy(ge);
-        if (g) (void)hipGraphDestroy(g);
-    };
-    try {
-        hipck(hipStreamBeginCapture(I.stream(), hipStreamCaptureModeThreadLocal), "begin capture");
-        try {
-            hipck(hipMemsetAsync(buf.p, 0, bytes, I.stream()), "clear stamps");
-            cycle_program();
-        } catch (...) {
-            (void)hipStreamEndCapture(I.stream(), &g);
-            throw;
-        }
-        hipck(hipStreamEndCapture(I.stream(), &g), "end capture");
-        hipck(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0), "instantiate");
-        const int64_t launches = I.stamp_q;
-        for (int r = 0; r < reps; ++r) {
-            hipck(hipGraphLaunch(ge, I.stream()), "graph launch");
-            hipck(hipStreamSynchronize(I.stream()), "sync");
-            hipck(hipMemcpy(host.data(), buf.p, bytes, hipMemcpyDeviceToHost), "read stamps");
-            for (int64_t q = 0; q < launches; ++q) {
-                const unsigned long long* st = host.data() + 2 * cap * q;
-                unsigned long long t0 = ~0ull, t1 = 0;
-                for (int64_t wv = 0; wv < cap; ++wv) {
-                    if (st[2 * wv] && st[2 * wv] < t0) t0 = st[2 * wv];
-                    if (st[2 * wv + 1] > t1) t1 = st[2 * wv + 1];
-                }
-                if (t0 == ~0ull || t1 <= t0) continue;  // another form ran at the site
-                const double ms = (double)(t1 - t0) / (double)khz;
-                total += ms;
-                ++count;
-                if (per_launch) per_launch->push_back(ms);
-            }
-        }
-    } catch (...) {
-        cleanup();
-        (void)hipGetLastError();
-        throw;
-    }
-    cleanup();
-    if (!count) throw StatusError(MPG_ERR_UNSUPPORTED, "no launch of the phase stored stamps");
-    return total / count;
-}
-
-// A phase kernel's share of the stream inside graph replays of the cycle
-// (which: 0 the Arnoldi SpMV in the form each step runs, 2 the CGS update, 3
-// the panel dots), from HIP events around whole replays: the cycle is
-// captured twice, as the solve runs it and with every launch of that phase
-// issued twice in a row, and the graphs are replayed alternately; the
-// difference of the replay times over the number of added launches is what
-// one launch adds to the cycle -- the kernel plus its dispatch and release,
-// with no marker packet near it (what rocprofv3's kernel duration measures).
-// The duplicates run on the state the first launch left: the SpMV and the
-// dots rewrite the same outputs; a second CGS update subtracts V h once more
-// (the basis stays normalised; an update that sums the dots' partials itself
-// gets the dots re-run ahead of it, whose own share is measured and taken
-// out). Measurement only, like time_phase_graph.
-double FusedEngine::time_phase_dup(int which, int reps, int64_t* launches) {
-    measured = true;
-    Impl& I = *p_;
-    if (!I.use_graph) throw StatusError(MPG_ERR_UNSUPPORTED, "the cycle is not captured (MPG_NO_GRAPH / eager ranks)");
-    if (which != 0 && which != 2 && which != 3) throw std::invalid_argument("phase: 0 spmv, 2 cgs update, 3 dots");
-    hipGraph_t g[2] = {nullptr, nullptr};
-    hipGraphExec_t ge[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    auto cleanup = [&] {
-        I.dup_phase = -1;
-        I.dup_step_only = false;
-        for (int q = 0; q < 2; ++q) {
-            if (ge[q]) (void)hipGraphExecDestroy(ge[q]);
-            if (g[q]) (void)hipGraphDestroy(g[q]);
-            if (ev[q]) (void)hipEventDestroy(ev[q]);
-        }
-    };
-    std::vector<double> diff;
-    int64_t added = 0, with_dots = 0, with_step = 0;
-    // (set by the correction run below for its own call only)
-    const bool step_only = I.dup_step_only;
-    I.dup_step_only = false;
-    try {
-        for (int q = 0; q < 2; ++q) {
-            I.dup_phase = q ? which : -1;
-            I.dup_step_only = q && step_only;
-            I.dup_count = 0;
-            I.dup_with_dots = 0;
-            I.dup_with_step = 0;
-            hipck(hipStreamBeginCapture(I.stream(), hipStreamCaptureModeThreadLocal), "begin capture");
-            try {
-                cycle_program();
-            } catch (...) {
-                (void)hipStreamEndCapture(I.stream(), &g[q]);
-                throw;
-            }
-            hipck(hipStreamEndCapture(I.stream(), &g[q]), "end capture");
-            hipck(hipGraphInstantiate(&ge[q], g[q], nullptr, nullptr, 0), "instantiate");
-            if (q) {
-                added = I.dup_count;
-                with_dots = I.dup_with_dots;
-                with_step = I.dup_with_step;
-            }
-        }
-        I.dup_phase = -1;
-        I.dup_step_only = false;
-        if (added < 1) throw StatusError(MPG_ERR_UNSUPPORTED, "the cycle has no launch of that phase");
-        for (hipEvent_t& e : ev) hipck(hipEventCreate(&e), "event");
-        for (int q = 0; q < 2; ++q) hipck(hipGraphLaunch(ge[q], I.stream()), "graph launch");  // warm
-        hipck(hipStreamSynchronize(I.stream()), "sync");
-        for (int r = 0; r < reps; ++r) {
-            float ms[2] = {0, 0};
-            for (int q = 0; q < 2; ++q) {
-                hipck(hipEventRecord(ev[0], I.stream()), "record");
-                hipck(hipGraphLaunch(ge[q], I.stream()), "graph launch");
-                hipck(hipEventRecord(ev[1], I.stream()), "record");
-                hipck(hipEventSynchronize(ev[1]), "sync");
-                hipck(hipEventElapsedTime(&ms[q], ev[0], ev[1]), "elapsed");
-            }
-            diff.push_back((double)(ms[1] - ms[0]) / (double)added);
-        }
-    } catch (...) {
-        cleanup();
-        (void)hipGetLastError();
-        throw;
-    }
-    cleanup();
-    if (launches) *launches = added;
-    std::sort(diff.begin(), diff.end());
-    double ms = diff[diff.size() / 2];
-    if (with_dots) ms -= time_phase_dup(3, reps) * (double)with_dots / (double)added;
-    if (with_step) {  // updates behind the SpMV + dots launch: that launch's share, measured on those steps alone
-        I.dup_step_only = true;
-        ms -= time_phase_dup(0, reps) * (double)with_step / (double)added;
-    }
-    return ms;
-}
+const CyclePolicy& FusedEngine::policy() const { return p_->pol; }
+const std::vector<Op>& FusedEngine::cycle_ops() const { return p_->cycle; }
+hipStream_t FusedEngine::stream() const { return p_->stream(); }
+mpg_ctx_t FusedEngine::ctx() const { return p_->ctx; }
 
 // ---------------------------------------------------------------- mpg_solve (fused)
 void fill_history(const FusedEngine& e, mpg_solve_result* r) {
@@ -1555,20 +1041,12 @@ int mpg_engine_create(const mpg_solve_args* a, mpg_engine_t* out, char* err, int
 
 int mpg_engine_run(mpg_engine_t e, int max_cycles, int* done) {
     if (!e || !e->eng) return MPG_ERR_ARG;
-    e->last_error.clear();
-    try {
-        mpg::ScopedContext scope(e->ctx);
+    return mpg::engine_call(e, [&] {
         bool d = false;
-        int ran = e->eng->run(max_cycles, d);
+        const int ran = e->eng->run(max_cycles, d);
         if (done) *done = d ? 1 : 0;
         return ran;
-    } catch (const mpg::StatusError& ex) {
-        e->last_error = ex.what();
-        return ex.status;
-    } catch (const std::exception& ex) {
-        e->last_error = ex.what();
-        return MPG_ERR_HIP;
-    }
+    });
 }
 
 const char* mpg_engine_last_error(mpg_engine_t e) { return e ? e->last_error.c_str() : ""; }
@@ -1580,103 +1058,16 @@ int mpg_engine_sync(mpg_engine_t e) {
 
 int64_t mpg_engine_total_iters(mpg_engine_t e) { return e && e->eng ? (int64_t)e->eng->total_iters() : -1; }
 
-int mpg_engine_time_phase(mpg_engine_t e, int which, int reps, double* avg_ms) {
-    if (!e || !e->eng || !avg_ms || reps < 1 || which < 0 || which > 3) return MPG_ERR_ARG;
-    try {
-        mpg::ScopedContext scope(e->ctx);
-        *avg_ms = e->eng->time_phase(which, reps);
-        return MPG_OK;
-    } catch (const std::exception&) {
-        return MPG_ERR_HIP;
-    }
-}
-
-int mpg_engine_time_spmv_incycle(mpg_engine_t e, int cycles, double* avg_ms, double* per_launch_ms, int cap) {
-    if (!e || !e->eng || !avg_ms || cycles < 1 || cap < 0 || (cap && !per_launch_ms)) return MPG_ERR_ARG;
-    try {
-        mpg::ScopedContext scope(e->ctx);
-        std::vector<double> t;
-        *avg_ms = e->eng->time_phase(0, cycles, true, &t);
-        for (size_t i = 0; i < t.size() && (int)i < cap; ++i) per_launch_ms[i] = t[i];
-        return (int)t.size();
-    } catch (const std::exception&) {
-        return MPG_ERR_HIP;
-    }
-}
-
-int mpg_engine_time_phase_dup(mpg_engine_t e, int which, int reps, double* avg_ms, int64_t* launches) {
-    if (!e || !e->eng || !avg_ms || reps < 1 || (which != 0 && which != 2 && which != 3)) return MPG_ERR_ARG;
-    e->last_error.clear();
-    try {
-        mpg::ScopedContext scope(e->ctx);
-        *avg_ms = e->eng->time_phase_dup(which, reps, launches);
-        return MPG_OK;
-    } catch (const mpg::StatusError& ex) {
-        e->last_error = ex.what();
-        return ex.status;
-    } catch (const std::exception& ex) {
-        e->last_error = ex.what();
-        return MPG_ERR_HIP;
-    }
-}
-
-int mpg_engine_time_phase_stamps(mpg_engine_t e, int which, int reps, double* avg_ms, double* per_launch_ms,
-                                 int cap) {
-    if (!e || !e->eng || !avg_ms || reps < 1 || cap < 0 || (cap && !per_launch_ms) ||
-        (which != 0 && which != 2 && which != 3))
-        return MPG_ERR_ARG;
-    e->last_error.clear();
-    try {
-        mpg::ScopedContext scope(e->ctx);
-        std::vector<double> t;
-        *avg_ms = e->eng->time_phase_stamps(which, reps, &t);
-        for (size_t i = 0; i < t.size() && (int)i < cap; ++i) per_launch_ms[i] = t[i];
-        return (int)t.size();
-    } catch (const mpg::StatusError& ex) {
-        e->last_error = ex.what();
-        return ex.status;
-    } catch (const std::exception& ex) {
-        e->last_error = ex.what();
-        return MPG_ERR_HIP;
-    }
-}
-
-int mpg_engine_time_phase_graph(mpg_engine_t e, int which, int reps, double* avg_ms, double* per_launch_ms,
-                                int cap) {
-    if (!e || !e->eng || !avg_ms || reps < 1 || cap < 0 || (cap && !per_launch_ms) ||
-        (which != 0 && which != 2 && which != 3))
-        return MPG_ERR_ARG;
-    e->last_error.clear();
-    try {
-        mpg::ScopedContext scope(e->ctx);
-        std::vector<double> t;
-        *avg_ms = e->eng->time_phase_graph(which, reps, &t);
-        for (size_t i = 0; i < t.size() && (int)i < cap; ++i) per_launch_ms[i] = t[i];
-        return (int)t.size();
-    } catch (const mpg::StatusError& ex) {
-        e->last_error = ex.what();
-        return ex.status;
-    } catch (const std::exception& ex) {
-        e->last_error = ex.what();
-        return MPG_ERR_HIP;
-    }
-}
-
 int mpg_engine_report(mpg_engine_t e, mpg_solve_result* r) {
     if (!e || !e->eng || !r) return MPG_ERR_ARG;
-    try {
-        mpg::ScopedContext scope(e->ctx);
+    const int st = mpg::engine_call(e, [&] {
         e->eng->sync();
         mpg::fill_history(*e->eng, r);
         e->eng->finish_report(r);
-        return MPG_OK;
-    } catch (const mpg::StatusError& ex) {
-        std::snprintf(r->message, sizeof r->message, "%s", ex.what());
-        return ex.status;
-    } catch (const std::exception& ex) {
-        std::snprintf(r->message, sizeof r->message, "%s", ex.what());
-        return MPG_ERR_HIP;
-    }
+        return (int)MPG_OK;
+    });
+    if (st) std::snprintf(r->message, sizeof r->message, "%s", e->last_error.c_str());
+    return st;
 }
 
 double mpg_engine_phase_bytes(mpg_engine_t e, int which) {
@@ -1707,7 +1098,7 @@ int mpg_engine_prologue_format(mpg_engine_t e) {
 
 int mpg_engine_givens_folded(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
-    return e->eng->givens_folded() ? 1 : 0;
+    return e->eng->policy().fold;
 }
 
 int mpg_engine_step_dots_steps(mpg_engine_t e) {
@@ -1715,9 +1106,15 @@ int mpg_engine_step_dots_steps(mpg_engine_t e) {
     return e->eng->step_dots_steps();
 }
 
+int mpg_engine_cycle_policy(mpg_engine_t e, mpg_cycle_policy* out) {
+    if (!e || !e->eng || !out) return MPG_ERR_ARG;
+    *out = e->eng->policy();
+    return MPG_OK;
+}
+
 int mpg_engine_step_dots_status(mpg_engine_t e, int k) {
     if (!e || !e->eng) return MPG_ERR_ARG;
-    return e->eng->step_dots_status(k);
+    return mpg_arnoldi_step_dots_supported(e->eng->arnoldi(), k);
 }
 
 int mpg_engine_comm_ranks(mpg_engine_t e) {

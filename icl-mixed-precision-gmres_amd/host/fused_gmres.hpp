@@ -14,14 +14,17 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "IterUtil.hpp"
+#include "cycle_plan.hpp"
 #include "mpgmres/arnoldi.h"
 #include "mpgmres/capi.h"
 #include "mpgmres/solve.h"
+#include "types_hip.hpp"
 
 namespace mpg {
 
@@ -78,6 +81,26 @@ struct DevMem {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
+void hipck(hipError_t e, const char* what);  // throws std::runtime_error on a HIP runtime error
+
+// What `build` issues on the stream, captured and instantiated: the graph
+// pair is owned here and destroyed on every path. The constructor throws
+// when the capture, the build or the instantiation fails (nothing is left
+// capturing and the runtime's error state is cleared).
+struct CapturedGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    CapturedGraph() = default;
+    CapturedGraph(hipStream_t s, const std::function<void()>& build);
+    ~CapturedGraph() { reset(); }
+    CapturedGraph(const CapturedGraph&) = delete;
+    CapturedGraph& operator=(CapturedGraph&& o) noexcept {
+        std::swap(graph, o.graph), std::swap(exec, o.exec);
+        return *this;
+    }
+    void reset();
+};
+
 class FusedEngine {
 public:
     // `rows`/`halo` describe the local row block of a partitioned matrix
@@ -96,18 +119,16 @@ public:
     double time_phase(int which, int reps, bool inplace = false, std::vector<double>* per_launch = nullptr);
     double time_phase_graph(int which, int reps, std::vector<double>* per_launch = nullptr);
     double time_phase_stamps(int which, int reps, std::vector<double>* per_launch = nullptr);
-    double time_phase_dup(int which, int reps, int64_t* launches = nullptr);
+    double time_phase_dup(int which, int reps, int64_t* launches = nullptr, bool step_dots_only = false);
     double phase_bytes(int which) const;
     mpg_arnoldi_t arnoldi() const;
     // mixed-half: what the fp16 cast of the Arnoldi values did (stats of
     // mpg_csr_half_values, capi.h; zeros in other modes)
     const int64_t* half_stats() const;
-    // the Givens step rides the next SpMV (MPG_FOLD_GIVENS, mpg_arnoldi_fold_pays)
-    bool givens_folded() const;
     int prec_fused() const;  // mpg_engine_prec_fused
     int step_dots_steps() const;       // steps of a cycle that run the SpMV inside the dots' launch
-    int step_dots_status(int k) const;  // mpg_arnoldi_step_dots_supported at step k
     void sync();
+    const CyclePolicy& policy() const;  // mpg_engine_cycle_policy
 
     // history (per restart / per step)
     std::vector<CycleRecord> cycles;
@@ -130,20 +151,18 @@ private:
     std::unique_ptr<Convergence<double, void>> conv_;
     void prologue();
     void step(int k, bool fold);
-    void reduce(int nc);
-    void allreduce_partials(int ncols);
-    void givens(int k);
-    template <class F>
-    void timed(int phase, F&& launch);
-    template <class F>
-    void dup(int phase, F&& launch);
-    void timed_end(int phase);
+    void issue(const Op& op);
+    void issue(const std::vector<Op>& ops);
+    // the phase timers (fused_timing.cpp) walk the cycle's op list themselves
+    const std::vector<Op>& cycle_ops() const;
+    hipStream_t stream() const;
+    mpg_ctx_t ctx() const;
+    void require_captured_phase(int which);
     void update(int k);
     void store_next_basis(int k);
     double orth_loss_step(size_t k);
     void read_report(int count);
     void wait_event(hipEvent_t ev, int64_t cycle, const char* what);
-    void cycle_program();
     void ensure_graph();
     void record_steps(int64_t i);
     int run_pipelined(int max_cycles, bool& done);
@@ -164,5 +183,24 @@ struct mpg_engine {
     std::unique_ptr<mpg::FusedEngine> eng;
     std::string last_error;  // the text of the last failed mpg_engine_run
 };
+
+namespace mpg {
+// A C-ABI call into the engine on its context: what `f` returns (>= 0), or
+// the status of what it threw, with the text kept for mpg_engine_last_error.
+template <class F>
+int engine_call(mpg_engine_t e, F&& f) {
+    e->last_error.clear();
+    try {
+        ScopedContext scope(e->ctx);
+        return f();
+    } catch (const StatusError& ex) {
+        e->last_error = ex.what();
+        return ex.status;
+    } catch (const std::exception& ex) {
+        e->last_error = ex.what();
+        return MPG_ERR_HIP;
+    }
+}
+}  // namespace mpg
 
 #endif  // MPGMRES_FUSED_GMRES_HPP

@@ -170,8 +170,10 @@ int mpg_arnoldi_givens_partials_spmv(mpg_arnoldi_t a, int k);
  * with the panel dots <v_j, w>, j <= k, formed in the same launch: replaces
  * spmv + dots ahead of mpg_arnoldi_cgs_partials (one GPU, CGS / CGSR,
  * k + 1 <= 32). MPG_ERR_UNSUPPORTED unless the SpMV runs on the SELL copy
- * with an fp32 basis, fp32 values, 16-bit columns and the v_k window. */
+ * with an fp32 basis, fp32 values, 16-bit columns and the v_k window.
+ * _supported returns the status the launch would, without launching. */
 int mpg_arnoldi_spmv_dots(mpg_arnoldi_t a, int k, int fold);
+int mpg_arnoldi_spmv_dots_supported(mpg_arnoldi_t a, int k);
 /* SpMV step k inside the panel dots' launch (fold as above): the dots' grid
  * of 1024-lane workgroups, each forming its own 4096 rows of w and v_k, then
  * the panel dots on them from LDS -- replaces spmv + dots ahead of

@@ -209,6 +209,54 @@ int mpg_engine_slices_per_wave(mpg_engine_t e);
 int mpg_engine_half_stats(mpg_engine_t e, int64_t* stats);
 int mpg_engine_destroy(mpg_engine_t e);
 
+/* ---- the fused engine's restart cycle as data ----
+ * What decides the launches of a cycle, resolved once when the engine is
+ * created (environment, ranks, preconditioner, what the workspace supports).
+ * Flags are 0 / 1 unless said. The per-step arrays hold the first
+ * MPG_CYCLE_POLICY_STEPS steps; a later step counts as unsupported (both
+ * launches stop at 32 columns). */
+#define MPG_CYCLE_POLICY_STEPS 128
+typedef struct {
+    int32_t ranks;        /* 0: one GPU, no communicator; else the ranks of the row-partitioned solve (1 included) */
+    int32_t orth;         /* mpg_orth_t */
+    int32_t m;            /* restart length */
+    int32_t graph;        /* the cycle is captured and replayed (MPG_NO_GRAPH, capturable collectives) */
+    int32_t pipeline;     /* cycles start with a snapshot of x (MPG_PIPELINE) */
+    int32_t fold;         /* Givens(k-1) rides SpMV(k) (MPG_FOLD_GIVENS; agreed across ranks) */
+    int32_t combine;      /* last-arriver combines (MPG_COMBINE) */
+    int32_t cgs_partials; /* the CGS update sums the dots' partials itself (MPG_CGS_PARTIALS) */
+    int32_t fuse_dots, fuse_dots_required, fuse_dots_k0; /* MPG_FUSE_DOTS (= 2: required), MPG_FUSE_DOTS_K0 */
+    int32_t step_dots;    /* MPG_STEP_DOTS: 0 never, 1 wherever supported, 2 required, -1 the steps lo <= k + 1 <= hi */
+    int32_t step_dots_lo, step_dots_hi;
+    int32_t sep_prec;          /* a preconditioner that is not applied inside the phase kernels (ILU, block Jacobi) */
+    int32_t sep_prec_step;     /* ... a launch of its own after every SpMV */
+    int32_t sep_prec_prologue; /* ... and after the residual prologue */
+    int32_t partials_max_cols; /* mpg_arnoldi_partials_max_cols() */
+    int32_t fold_max_m;        /* mpg_arnoldi_fold_max_m() */
+    uint8_t step_dots_ok[MPG_CYCLE_POLICY_STEPS]; /* mpg_arnoldi_step_dots_supported(k) == MPG_OK */
+    uint8_t spmv_dots_ok[MPG_CYCLE_POLICY_STEPS]; /* mpg_arnoldi_spmv_dots_supported(k) == MPG_OK */
+} mpg_cycle_policy;
+/* The launches and collectives of one restart cycle under `p`, in order, as
+ * text: one token per op, separated by single spaces, NUL-terminated and cut
+ * at len - 1 characters. Returns the length the whole text needs (without
+ * the NUL), or a status < 0: MPG_ERR_UNSUPPORTED (-5) where a required
+ * launch (step_dots / fuse_dots = 2) cannot be taken, MPG_ERR_ARG (-2).
+ * A token is name, name(a) or name(a,b) -- the step k, then the pass, the
+ * column j, the fold form or the column count: x_snapshot halo(k) halo(x)
+ * allreduce_partials+halo(k) spmv(k) givens+spmv(k) spmv_dots(k,f)
+ * step_dots(k,f) apply_prec(wK) dots(k) dots_sums(k) allreduce_partials(nc)
+ * reduce(nc) allreduce_sums(nc) cgs_partials(k) cgs(k,pass)
+ * cgs_givens(k,pass) cgsr_wide_pass(k,pass) mgs_partials(k,j) givens(k)
+ * givens_partials(k) update(k) prologue prologue_wnorm prologue_finish
+ * prologue_finish_partials -- followed, where the op is a site of the phase
+ * timers, by @P (P as `which` of mpg_engine_time_phase: 0 SpMV, 1 prologue,
+ * 2 CGS update, 3 dots), then +dup where mpg_engine_time_phase_dup issues it
+ * twice, then <D where the op D tokens back is issued again ahead of the
+ * duplicate: "cgs_partials(3)@2+dup<1". */
+int mpg_cycle_plan_describe(const mpg_cycle_policy* p, char* buf, int len);
+/* the resolved policy of a live engine */
+int mpg_engine_cycle_policy(mpg_engine_t e, mpg_cycle_policy* out);
+
 /* process-wide counts of the operator-surface driver's cycle programs
  * (CycleProgram<Hip>, types_hip.hpp): cycles recorded into a graph, cycles
  * replayed from one, and recordings voided by a step that must read the

@@ -148,3 +148,31 @@ def test_measurement_hooks(mpg, monkeypatch):
             split.close()
     finally:
         eng.close()
+
+
+def test_cycle_policy_of_live_engines(mpg, monkeypatch):
+    """The resolved policy of a default engine (mpg_engine_cycle_policy): the
+    fp32 class may take the one launch at every step of BAND's cycle and folds
+    the Givens step, the fp64 class may take it at none; and the plan that
+    policy describes holds as many SpMV + dots launches as the layout reports."""
+    import ctypes as C
+    for var in ("MPG_STEP_DOTS", "MPG_STEP_DOTS_LO", "MPG_STEP_DOTS_HI", "MPG_FOLD_GIVENS"):
+        monkeypatch.delenv(var, raising=False)
+    A, xt, b = _problem(mpg, 13_316)
+    for accum in ("f32", "f64"):
+        eng = mpg.Engine(A, b, xt, mode="mixed", orth="cgs", prec="identity", rlen=30, tol=0.0, max_restarts=1,
+                         accum=accum)
+        try:
+            p = eng.cycle_policy()
+            assert (p.m, p.ranks, p.orth, p.step_dots) == (30, 0, 0, -1)
+            if accum == "f32":
+                assert all(p.step_dots_ok[k] == 1 for k in range(30)) and p.fold == 1
+            else:
+                assert not any(p.step_dots_ok)
+            buf = C.create_string_buffer(1 << 14)
+            assert 0 < mpg.host_lib().mpg_cycle_plan_describe(C.byref(p), buf, len(buf)) < len(buf)
+            plan = buf.value.decode().split(" ")
+            fused = sum(t.startswith("step_dots(") for t in plan)
+            assert fused == eng.spmv_layout().get("dots_fused", 0) == (30 if accum == "f32" else 0)
+        finally:
+            eng.close()
