@@ -1316,25 +1316,30 @@ __global__ __launch_bounds__(BS) void k_dots_nc(int n, const T* __restrict__ V, 
 // values, the uniform pair storage with the v_k window; one pass: n <= 4096
 // kCombineGroups, n % 4 == 0). The grid and the row ownership are k_dots_nc's:
 // workgroup b (1024 threads) owns rows [4096 b, 4096 b + 4096), lane t the row
-// group 4 (1024 b + t) -- 64 whole SELL-64 slices, four per wave. The
-// workgroup forms v_k = T(w_prev * inv) for its rows and 64 on either side in
-// one LDS window (every gather of its slices falls inside), runs
-// k_step_sell2's row sums on it, stores w and v_k, and leaves its rows of w in
-// LDS beside the window. dots_panel then runs on the staged w and v_k and the
+// group 4 (1024 b + t) -- 64 whole SELL-64 slices, four per wave. Each wave
+// forms v_k = T(w_prev * inv) for its 256 rows and 64 on either side in an
+// LDS window of its own (every gather of its slices falls inside; the rows
+// beside its own are the neighbouring wave's, scaled again by the same
+// operation), runs k_step_sell2's row sums on it, stores w and v_k, and leaves
+// its rows of w in LDS. dots_panel then runs on the staged w and v_k and the
 // global V(:, 0..k-1): the same products, the same order and the same Gd
 // partials per column as k_dots_nc after k_step_sell2, with no second launch
 // and no re-read of w and v_k. PF: the lane's first batch of earlier columns
 // is issued behind the slices' loads, so its latency runs under the row sums.
-// FOLD as in k_step_sell2: every workgroup sums the <= kBlock ||w||^2
-// partials in waves 0..3 in the same fixed order (the other waves hold none).
+// FOLD: every wave sums the <= kBlock ||w||^2 partials itself, with the
+// butterflies and in the order of k_step_sell2's waves 0..3.
+// The waves of a workgroup do not wait for one another before the partial
+// combine at the end (store_partials): with the three workgroup barriers this
+// kernel first had (the fold, one shared window, the hand-off to the dots)
+// the earliest wave waited for the latest three times over.
 constexpr int kStepDotsRows = 4 * kCombineBlock;  // rows of a workgroup
 
 template <class T, class A, int HELD>
 struct DotsStaged {
     static constexpr bool kStaged = true;
     static constexpr int kHeld = HELD;
-    const T* wst;   // LDS: w of this workgroup's rows
-    const T* vkst;  // LDS: v_k of this workgroup's rows
+    const T* wst;   // LDS: w of this wave's rows
+    const T* vkst;  // LDS: v_k of this wave's rows
     int base;       // its first row
     Raw4<T> held[HELD > 0 ? HELD : 1];
     __device__ __forceinline__ void load_w(int i, A (&wv)[4]) const { Row4<T>::load(wst + (i - base), wv); }
@@ -1344,6 +1349,26 @@ struct DotsStaged {
         return r;
     }
 };
+
+// LDS written by a wave and read back by other lanes of the same wave: the
+// wave's own LDS operations complete (lgkmcnt(0); vmcnt and expcnt untouched,
+// so loads issued ahead stay in flight), and neither the compiler nor the
+// hardware moves an LDS access across.
+__device__ __forceinline__ void wave_lds_handoff() {
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    wave_lds_sync();
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+}
+
+// lane 0's value in every lane (wave_sum's result), as a wave-uniform value
+__device__ __forceinline__ float wave_first(float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+__device__ __forceinline__ double wave_first(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                            __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
 
 template <class T, class P, int W, bool FOLD, int BE, int NC, bool PF, class A>
 __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices, const int16_t* __restrict__ col,
@@ -1358,40 +1383,55 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
     static_assert(std::is_same_v<T, float>, "fp32 basis and values");
     using CI = int16_t;
     using Row = SellRow<T, CI, W, (MPG_SELL_NT != 0), BE>;
-    constexpr int BS = kCombineBlock, SPW = 4;
-    constexpr int RB = kStepDotsRows, WL = kWinLo + RB + kWinHi;  // the workgroup's window of v_k
-    static_assert(SPW * (BS / kWave) * kWave == RB, "four slices per wave cover the workgroup's rows");
-    __shared__ __attribute__((aligned(16))) T win[WL];
+    constexpr int BS = kCombineBlock, SPW = 4, NW = BS / kWave;
+    constexpr int RB = kStepDotsRows, RW = SPW * kWave;  // rows of the workgroup, of a wave
+    constexpr int WL = kWinLo + RW + kWinHi;             // a wave's window of v_k
+    // The wave's four slices are the rows its lanes take in dots_panel_from:
+    // wave wid owns slices s0..s0+3 = rows [base + RW wid, base + RW wid + RW),
+    // and lane `lane` of that wave reads the row group base + 4 (kWave wid +
+    // lane) of w and v_k there. So both go from the SpMV phase to the dots
+    // inside one wave, and no wave waits for another before the final combine.
+    static_assert(NW * RW == RB, "four slices per wave cover the workgroup's rows");
+    static_assert(RW == 4 * kWave, "a wave's slices are its lanes' row groups of dots_panel_from");
+    __shared__ __attribute__((aligned(16))) T win[NW][WL];
     __shared__ __attribute__((aligned(16))) T wst[RB];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = wave_id();
     const int base = (int)blockIdx.x * RB;
+    const int row0 = base + wid * RW;  // the wave's first row
     const int s0 = (int)blockIdx.x * (RB / kWave) + wid * SPW;
     // 0. the slices' offsets (computed) and pattern indices
     Row row[SPW];
     bool live_p[SPW];
 #pragma unroll
     for (int p = 0; p < SPW; ++p) {
-        live_p[p] = s0 + p < nslices;  // a dead wave still joins every barrier
+        live_p[p] = s0 + p < nslices;  // (a dead wave runs on slice 0's addresses and reaches the final combine)
         row[p].init_uniform(live_p[p] ? s0 + p : 0, ustride, spat, coff);
     }
     __builtin_amdgcn_sched_barrier(0);
-    // 1. the fold's ||w||^2 partial: one per lane of the first kBlock lanes
-    A part = A(0);
+    // 1. the fold's ||w||^2 partials: lane l of every wave holds those of
+    // lane l of the waves 0..NG-1 of a kBlock workgroup
+    constexpr int NG = kBlock / kWave;
+    A part[NG];
     if constexpr (FOLD) {
-        part = (A)fold.norm2[tid < fold.nparts ? tid : 0];
-        if (tid >= fold.nparts) part = A(0);
+#pragma unroll
+        for (int q = 0; q < NG; ++q) {
+            const int t = q * kWave + lane;
+            part[q] = (A)fold.norm2[t < fold.nparts ? t : 0];
+            if (t >= fold.nparts) part[q] = A(0);
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
-    // 2. the window of w_prev, raw: the lane's own row group and, in the
-    // first 128 lanes, one entry of the 64 rows on either side (clamped
-    // addresses; n % 4 == 0, so a row group lies inside [0, n) or outside)
+    // 2. the wave's window of w_prev, raw: the lane's own row group and one
+    // entry each of the 64 rows below and above the wave's (clamped addresses;
+    // n % 4 == 0, so a row group lies inside [0, n) or outside)
     const int i4 = base + 4 * tid;
     const bool in4 = i4 < n;
     Raw4<T> wr;
     wr.load(wprev + (in4 ? i4 : 0));
-    const int hc = tid < kWinLo ? base - kWinLo + tid : base + RB + (tid - kWinLo);
-    const bool hin = tid < kWinLo + kWinHi && hc >= 0 && hc < n;
-    const T wh = wprev[hin ? hc : 0];
+    const int clo = row0 - kWinLo + lane, chi = row0 + RW + lane;
+    const bool lo_in = clo >= 0 && clo < n, hi_in = chi < n;
+    const T wlo = wprev[lo_in ? clo : 0];
+    const T whi = wprev[hi_in ? chi : 0];
     __builtin_amdgcn_sched_barrier(0);
     // 3. the slices' first batches: values first, then the columns
 #pragma unroll
@@ -1411,10 +1451,11 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
     // (with the fold 6 columns: 8 held across the partial sums spilled, 20-28 B per lane)
     constexpr int HMAX = FOLD ? 6 : B;
     constexpr int HELD = !PF ? 0 : NC - 1 < HMAX ? NC - 1 : HMAX;
+    T* const wwin = win[wid];  // the wave's own rows sit at wwin + kWinLo
     DotsStaged<T, A, HELD> src;
-    src.wst = wst;
-    src.vkst = win + kWinLo;
-    src.base = base;
+    src.wst = wst + wid * RW;
+    src.vkst = wwin + kWinLo;
+    src.base = row0;
     if constexpr (HELD > 0) {
 #pragma unroll
         for (int u = 0; u < HELD; ++u) src.held[u].load(V + (int64_t)u * ld + (in4 ? i4 : 0));
@@ -1423,25 +1464,16 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
     T inv;
     double nrm2sq = 0.0;
     if constexpr (FOLD) {
-        constexpr int NG = kBlock / kWave;  // the waves that hold partials
-        __shared__ A scratch[NG];
-        __shared__ T inv_s;
+        // (the same value in every wave and lane: workgroup 0 hands any of them to givens_block)
         if (fold.nparts > 0) {
-            if (wid < NG) {
-                const A v = wave_sum(part + A(0));
-                if (lane == 0) scratch[wid] = v;
-            }
-            lds_barrier();
             A r = A(0);
 #pragma unroll
-            for (int q = 0; q < NG; ++q) r += scratch[q];
+            for (int q = 0; q < NG; ++q) r += wave_first(wave_sum(part[q] + A(0)));
             nrm2sq = (double)r;
         } else {
             nrm2sq = fold.norm2[0];
         }
-        if (tid == 0) inv_s = inv_of_norm2<T>(nrm2sq);
-        lds_barrier();
-        inv = inv_s;
+        inv = inv_of_norm2<T>(nrm2sq);
     } else {
         inv = *inv_p;
     }
@@ -1450,11 +1482,12 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
         T vq[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) vq[r] = in4 ? (T)(wr.template at<T>(r) * inv) : T(0);
-        Row4<T>::store(win + kWinLo + 4 * tid, vq);
-        if (tid < kWinLo + kWinHi) win[tid < kWinLo ? tid : RB + tid] = hin ? (T)(wh * inv) : T(0);
+        Row4<T>::store(wwin + kWinLo + 4 * lane, vq);
+        wwin[lane] = lo_in ? (T)(wlo * inv) : T(0);
+        wwin[kWinLo + RW + lane] = hi_in ? (T)(whi * inv) : T(0);
     }
-    lds_barrier();
-    auto xv = [&](int c) { return (double)win[c - base + kWinLo]; };
+    wave_lds_handoff();  // the window is the wave's own
+    auto xv = [&](int c) { return (double)wwin[c - row0 + kWinLo]; };
     A sum[SPW] = {};
 #pragma unroll
     for (int p = 0; p < SPW; ++p)
@@ -1472,11 +1505,11 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
             const T t = (T)sum[p];  // spmv(1, A, v, 0, w): y = 1*t
             wi = precond<T, P>(t, diag, i);
             w[i] = wi;
-            V[(int64_t)k * ld + i] = win[i - base + kWinLo];
+            V[(int64_t)k * ld + i] = wwin[i - row0 + kWinLo];
         }
         wst[i - base] = wi;  // rows past n: an exact 0, and no row group of theirs is read
     }
-    lds_barrier();
+    wave_lds_handoff();  // the wave's rows of w and v_k go to its own lanes (the identity above)
     dots_panel_from<T, BS, NC, A>(n, V, ld, src, dpart);
     if constexpr (FOLD) {
         __shared__ T col_s[kFoldMaxM + 2], c_s[kFoldMaxM + 2], s_s[kFoldMaxM + 2];
