@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (ACCUMS, ENGINES, MODES, ORTHS, PRECS, SPMV_FORMATS, STATUS, CondestResult, CyclePolicy, HostCsr, RankLayout, SolveArgs,
+from ._abi import (ACCUMS, ENGINES, MODES, ORTHS, PRECS, SPMV_FORMATS, STATUS, ArnoldiDesc, CondestResult, CyclePolicy, HostCsr, RankLayout, SolveArgs,
                    SolveResult, condest_args, condest_dict)
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -210,6 +210,7 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_cycle_plan_describe.argtypes = [C.POINTER(CyclePolicy), C.c_char_p, C.c_int]
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_fused.argtypes = [C.c_void_p]
+    lib.mpg_engine_prec_sweeps.argtypes = [C.c_void_p]
     lib.mpg_engine_prologue_format.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.restype = C.c_int64
@@ -288,6 +289,19 @@ _HIP_DECLS.update({
     "mpg_bjacobi_apply_f64": ([_P, _I64, _I32, _P, _P], C.c_int),
     "mpg_bjacobi_apply_f32": ([_P, _I64, _I32, _P, _P], C.c_int),
     "mpg_bjacobi_apply_f64_p32": ([_P, _I64, _I32, _P, _P], C.c_int),
+    "mpg_csr_jacobi_sweep_f64": ([_P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "mpg_csr_jacobi_sweep_f32": ([_P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "mpg_sell_jacobi_sweep_f64": ([_P, _P, _P, _P, _P, _P], C.c_int),
+    "mpg_sell_jacobi_sweep_f32": ([_P, _P, _P, _P, _P, _P], C.c_int),
+    "mpg_arnoldi_neumann_apply": ([_P, _I32, _P, _P, _P], C.c_int),
+    "mpg_arnoldi_create": ([_P, _P, C.POINTER(_P)], C.c_int),
+    "mpg_arnoldi_destroy": ([_P], C.c_int),
+    "mpg_arnoldi_set_accum": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_spmv": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_wprev_dev": ([_P, C.c_int], _P),
+    "mpg_arnoldi_inv_dev": ([_P], _P),
+    "mpg_arnoldi_spmv_layout": ([_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64),
+                                 C.POINTER(_I32)], C.c_int),
     "mpg_nrm2_pair_host": ([_P, _I64, C.c_int, _P, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)],
                            C.c_int),
 })
@@ -914,18 +928,22 @@ class Engine:
         reports "dots_fused": the number of such steps per cycle (the key is
         absent when there are none). With prec="bjacobi" it reports
         "prec_fused": 1 when the block apply runs inside the SpMV launches, 0
-        when it is a launch of its own (mpg_engine_prec_fused)."""
+        when it is a launch of its own (mpg_engine_prec_fused). With
+        prec="neumann" it reports "prec_sweeps": the Jacobi sweeps per
+        application (mpg_engine_prec_sweeps)."""
         f, w, cb, st, win = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         if self._lib.mpg_engine_spmv_layout(self._h, C.byref(f), C.byref(w), C.byref(cb), C.byref(st), C.byref(win)):
             raise RuntimeError("mpg_engine_spmv_layout failed")
         fused = int(self._lib.mpg_engine_step_dots_steps(self._h))
         pf = int(self._lib.mpg_engine_prec_fused(self._h))
+        ps = int(self._lib.mpg_engine_prec_sweeps(self._h))
         return {**({"dots_fused": fused} if fused > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
                 "stored": st.value, "window": bool(win.value),
                 "slices_per_wave": int(self._lib.mpg_engine_slices_per_wave(self._h)),
                 "givens_folded": bool(self._lib.mpg_engine_givens_folded(self._h) == 1),
                 "accum": {0: "f64", 1: "f32"}[int(self._lib.mpg_engine_accum(self._h))],
                 **({"prec_fused": pf} if pf >= 0 else {}),
+                **({"prec_sweeps": ps} if ps >= 0 else {}),
                 "prologue": {1: "csr", 2: "sell", 3: "node"}[int(self._lib.mpg_engine_prologue_format(self._h))]}
 
     def step_dots_status(self, k: int) -> int:

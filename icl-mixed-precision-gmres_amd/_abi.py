@@ -6,7 +6,7 @@ import ctypes as C
 
 MODES = {"mixed": 0, "baseline": 1, "single-prec": 2, "single": 3, "mixed-half": 4}
 ORTHS = {"cgs": 0, "mgs": 1, "cgsr": 2}
-PRECS = {"ilu": 0, "ilu_jacobi": 1, "jacobi": 2, "identity": 3, "bjacobi": 4}
+PRECS = {"ilu": 0, "ilu_jacobi": 1, "jacobi": 2, "identity": 3, "bjacobi": 4, "neumann": 5}
 ENGINES = {"surface": 0, "fused": 1}
 SPMV_FORMATS = {"auto": 0, "csr": 1, "sell": 2, "node": 3}
 ACCUMS = {"f64": 0, "f32": 1}  # mpg_solve_args.accum (MPG_ACCUM_F64 / MPG_ACCUM_F32, arnoldi.h)
@@ -162,4 +162,14 @@ class CyclePolicy(C.Structure):
         "sep_prec_step", "sep_prec_prologue", "partials_max_cols", "fold_max_m")] + [
         ("step_dots_ok", C.c_uint8 * CYCLE_POLICY_STEPS),
         ("spmv_dots_ok", C.c_uint8 * CYCLE_POLICY_STEPS),
+    ]
+
+
+class ArnoldiDesc(C.Structure):
+    """mpg_arnoldi_desc (arnoldi.h): what mpg_arnoldi_create builds a workspace from."""
+    _fields_ = [(f, C.c_int32) for f in (
+        "n", "n_ext", "m", "orth", "vec_type", "outer_type", "prec_type", "inner_val", "jacobi")] + [
+        ("A", C.c_void_p), ("val_outer", C.c_void_p), ("val_inner", C.c_void_p), ("diag", C.c_void_p),
+        ("b", C.c_void_p), ("x", C.c_void_p), ("spmv_format", C.c_int32), ("n_front", C.c_int32),
+        ("inner_row_exp", C.c_void_p), ("block_dinv", C.c_void_p), ("prec_block", C.c_int32),
     ]

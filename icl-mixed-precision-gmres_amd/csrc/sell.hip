@@ -866,12 +866,6 @@ void sell_free(SellCopy& S) {
 
 }  // namespace mpg
 
-struct mpg_sell {
-    mpg_ctx* ctx = nullptr;
-    int cols = 0;
-    SellCopy S;  // owns all its device memory (the flagged slices' rows included)
-};
-
 namespace {
 
 template <class X, class St, bool NORM = false>

@@ -342,6 +342,17 @@ struct SellCopy {
     int col_bytes() const { return c16 || c16s ? 2 : 4; }
 };
 
+}  // namespace mpg
+
+// The stand-alone copy behind mpg_sell_t (capi.h; sell.hip, neumann.hip)
+struct mpg_sell {
+    mpg_ctx* ctx = nullptr;
+    int cols = 0;
+    mpg::SellCopy S;  // owns all its device memory (the flagged slices' rows included)
+};
+
+namespace mpg {
+
 // Build the copy from the CSR structure and `val` (vtype; F16 = raw IEEE
 // half bits). format: 0 auto (only when padding adds <= 20 % to the stored
 // entries), 1 never, 2 always. Synchronises the context's stream.

@@ -138,6 +138,17 @@ struct FusedEngine::Impl {
     // 54: 6 waves per SIMD instead of 8), point Jacobi 451
     // (profiles/r08_bjacobi/bjacobi_bench.json)
     bool bj_fused_step = false, bj_fused_prologue = false;
+    // Jacobi-sweep polynomial (prec neumann): nm_steps sweeps on A z = w from
+    // z = 0 with Jacobi's inverse diagonal (`diag`), on the workspace's Arnoldi
+    // matrix (mpg_arnoldi_neumann_apply), in the slot ILU's solves take.
+    // One sweep is point Jacobi and runs as point Jacobi: the product inside
+    // the SpMV and the prologue (nm_steps stays 0), so that it has prec jacobi's
+    // bits in every class -- the launch of its own would sum the prologue's
+    // ||w||^2 in prologue_wnorm's order, other last bits under an fp64 Arnoldi.
+    int nm_steps = 0;   // sweeps applied between the phase kernels; 0: none (another preconditioner, or one sweep)
+    int nm_asked = 0;   // jacobi_steps of prec neumann; 0: another preconditioner
+    DevMem nm_work0, nm_work1;
+    bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || nm_asked == 1; }
     bool orthloss = false;    // LostOrthogonality: v_{k+1} stored each step, S / u below
     DevMem loss_S, loss_u;    // (m+1) x (m+1) and m+2 of T, zero-filled (IterUtil.hpp:185-191)
 
@@ -181,10 +192,14 @@ struct FusedEngine::Impl {
         check(st, "block Jacobi apply", ctx);
     }
     // M^-1 w for the preconditioners applied between the phase kernels: block
-    // Jacobi, or ILU with typesafe_apply's casts when the preconditioner
+    // Jacobi, the Jacobi sweeps, or ILU with typesafe_apply's casts when the preconditioner
     // precision differs (gmres.cpp:12-22)
+    void apply_neumann(void* w) {
+        check(mpg_arnoldi_neumann_apply(arn, nm_steps, w, nm_work0.p, nm_work1.p), "Jacobi-sweep apply", ctx);
+    }
     void apply_ilu(void* w) {
         if (bj_bs) return apply_bjacobi(w);
+        if (nm_steps) return apply_neumann(w);
         void* wp = w;
         if (ty.P != ty.T) {
             cast(w, ty.T, tmp_p.p, ty.P, n);
@@ -211,9 +226,9 @@ void FusedEngine::Impl::resolve_policy() {
     P.ranks = comm ? comm->size() : 0;
     P.orth = orth;
     P.m = m;
-    P.sep_prec = ilu || bj_bs;  // a preconditioner applied between the phase kernels, not inside them
-    P.sep_prec_step = ilu || (bj_bs && !bj_fused_step);
-    P.sep_prec_prologue = ilu || (bj_bs && !bj_fused_prologue);
+    P.sep_prec = ilu || bj_bs || nm_steps;  // a preconditioner applied between the phase kernels, not inside them
+    P.sep_prec_step = ilu || (bj_bs && !bj_fused_step) || nm_steps;
+    P.sep_prec_prologue = ilu || (bj_bs && !bj_fused_prologue) || nm_steps;
     P.partials_max_cols = mpg_arnoldi_partials_max_cols();
     P.fold_max_m = mpg_arnoldi_fold_max_m();
     for (int k = 0; k < std::min(m, MPG_CYCLE_POLICY_STEPS); ++k) {
@@ -284,7 +299,8 @@ void FusedEngine::Impl::resolve_policy() {
     if (int st = plan_cycle(P, cycle))
         throw StatusError(st, "MPG_STEP_DOTS=2 / MPG_FUSE_DOTS=2: a step of the cycle cannot take the required SpMV + "
                               "dots launch (one GPU, plain CGS with in-launch sums, no preconditioner launch -- ILU, "
-                              "block Jacobi -- between the SpMV and the dots, storage the launch supports)");
+                              "block Jacobi, Jacobi sweeps -- between the SpMV and the dots, storage the launch "
+                              "supports)");
 }
 
 FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int n_ext, int n_front)
@@ -306,8 +322,19 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     if (ilu && comm)
         throw std::invalid_argument("ILU / ILU-Jacobi factor the whole matrix: not available on a row-partitioned solve");
     const bool bjacobi = a.prec == MPG_PREC_BLOCK_JACOBI;
-    if (!ilu && !bjacobi && a.prec != MPG_PREC_IDENTITY && a.prec != MPG_PREC_JACOBI)
+    const bool neumann = a.prec == MPG_PREC_NEUMANN;
+    if (!ilu && !bjacobi && !neumann && a.prec != MPG_PREC_IDENTITY && a.prec != MPG_PREC_JACOBI)
         throw std::invalid_argument("Unknown prec type");
+    if (neumann) {
+        check_neumann_args(a);
+        if (comm)
+            throw StatusError(MPG_ERR_UNSUPPORTED,
+                              "prec neumann is not available on a row-partitioned solve: every sweep needs a halo "
+                              "exchange of z (the follow-up that would make it the first preconditioner stronger than "
+                              "Jacobi on more than one GPU)");
+        I.nm_asked = a.jacobi_steps;
+        I.nm_steps = a.jacobi_steps > 1 ? a.jacobi_steps : 0;
+    }
     if (bjacobi) {
         const int bs = a.prec_block == 0 ? 3 : a.prec_block;
         if (bs < 2 || bs > 4) throw std::invalid_argument("prec bjacobi: prec_block must be 2, 3 or 4 (0: 3)");
@@ -382,7 +409,7 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     // converted to float (types.hpp:393-431 on SparseMatrix<P>)
     // (max row sum all-reduced across ranks: ||A||_inf of the whole matrix)
     I.scal = DevMem(ctx, 64);
-    if (a.prec == MPG_PREC_JACOBI) {
+    if (a.prec == MPG_PREC_JACOBI || neumann) {
         I.diag = DevMem(ctx, (size_t)I.n * dsize(ty.P) + 16);
         double* rowmax = I.scal.as<double>() + 4;
         if (ty.P == MPG_F64) {
@@ -439,7 +466,7 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
             I.cast(I.tmp_t.p, ty.T, I.tmp_p.p, ty.P, I.n);
         }
         void* wp = ty.P != ty.T ? I.tmp_p.p : I.tmp_t.p;
-        if (a.prec == MPG_PREC_JACOBI) {
+        if (I.jacobi_inside()) {
             if (ty.P == MPG_F64)
                 check(mpg_gdmv_f64(ctx, I.n, 1.0, I.diag.as<double>(), (double*)wp, 0.0, (double*)wp), "gdmv", ctx);
             else
@@ -474,11 +501,13 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     d.outer_type = ty.X;
     d.prec_type = ty.P;
     d.inner_val = ty.VI;
-    d.jacobi = a.prec == MPG_PREC_JACOBI;
+    d.jacobi = I.jacobi_inside();
     d.A = I.csr;
     d.val_outer = I.val_outer;
     d.val_inner = I.val_inner;
-    d.diag = d.jacobi ? I.diag.p : nullptr;
+    // (the sweeps' diagonal rides in the descriptor with jacobi = 0: the phase
+    // kernels apply no preconditioner, mpg_arnoldi_neumann_apply reads it)
+    d.diag = d.jacobi || neumann ? I.diag.p : nullptr;
     d.b = I.b.p;
     d.x = I.xp;
     d.spmv_format = a.spmv_format;
@@ -497,6 +526,12 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     I.bj_fused_prologue = mpg_arnoldi_prec_fused(I.arn, 1) == 1;
     // fp32 Arnoldi: the reference's fp32 accumulation class on request (arnoldi.h)
     if (a.accum) check(mpg_arnoldi_set_accum(I.arn, MPG_ACCUM_F32), "mpg_arnoldi_set_accum", ctx);
+    if (I.nm_steps) {  // ||M^-1 b|| through the launches every application takes (tmp_t still holds T(b))
+        if (I.nm_steps >= 2) I.nm_work0 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
+        if (I.nm_steps >= 3) I.nm_work1 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
+        I.apply_neumann(I.tmp_t.p);
+        minvb_norm = I.nrm2(I.tmp_t.p, ty.T, I.n);
+    }
     // ranks all-reduce per-workgroup partials in place: same count on every rank
     // (MPG_UNIFORM_GROUPS=1 gives one GPU the ranks' partial counts: a P = 1
     // RCCL solve then has the single-GPU solve's bits, tests/test_dist_gpu.py)
@@ -920,13 +955,17 @@ double FusedEngine::phase_bytes(int which) const {
     // Jacobi's diagonal read inside the launch; block Jacobi's own launch
     // after it (w read and written again, bs inverse entries per row)
     const bool bjf = which == 1 ? I.bj_fused_prologue : I.bj_fused_step;
-    const double jac = I.args.prec == MPG_PREC_JACOBI ? 1.0 : I.bj_bs ? (bjf ? 0.0 : 2 * sT / sP) + I.bj_bs : 0.0;
+    const double jac = I.jacobi_inside() ? 1.0 : I.bj_bs ? (bjf ? 0.0 : 2 * sT / sP) + I.bj_bs : 0.0;
+    // the Jacobi sweeps' launches after the SpMV: the gdmv (w read, z written,
+    // the diagonal), then per sweep the matrix again, z read and written and
+    // three more n-vectors (r, the diagonal, z's own entry)
+    const double nm = I.nm_steps ? (2 * sT + sP) * n + (I.nm_steps - 1) * (z * (sV + 4) + (n + 1) * 4 + 5 * n * sT) : 0.0;
     if (which == 0) {
         // SURVEY §8(d) B_spmv, the same for every storage: CSR values + int32
         // columns + row pointers, x read once, y written (the SELL-64 copy
         // moves fewer bytes; profiles/ PMC traffic shows the actual ones),
         // plus the Jacobi diagonal when the preconditioner is fused in
-        return z * (sV + 4) + (n + 1) * 4 + 2 * n * sT + jac * n * sP;
+        return z * (sV + 4) + (n + 1) * 4 + 2 * n * sT + jac * n * sP + nm;
     }
     if (which == 1) return z * (sX + 4) + (n + 1) * 4 + 3 * n * sX + n * sT + jac * n * sP;
     if (which == 4) {
@@ -964,6 +1003,7 @@ double FusedEngine::phase_bytes(int which) const {
 mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
 int FusedEngine::prec_fused() const { return p_->bj_bs ? (p_->bj_fused_step ? 1 : 0) : -1; }
+int FusedEngine::prec_sweeps() const { return p_->nm_asked ? p_->nm_asked : -1; }
 int FusedEngine::step_dots_steps() const {
     return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::StepDots; });
 }
@@ -1086,6 +1126,7 @@ int mpg_engine_sell_columns(mpg_engine_t e, int32_t* form, int64_t* csr_slices, 
 }
 
 int mpg_engine_prec_fused(mpg_engine_t e) { return e && e->eng ? e->eng->prec_fused() : -1; }
+int mpg_engine_prec_sweeps(mpg_engine_t e) { return e && e->eng ? e->eng->prec_sweeps() : -1; }
 int mpg_engine_accum(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return mpg_arnoldi_accum(e->eng->arnoldi());

@@ -16,6 +16,7 @@
 
 #include <functional>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -27,6 +28,24 @@
 #include "types_hip.hpp"
 
 namespace mpg {
+
+// prec neumann (MPG_PREC_NEUMANN): the sweep count and the modes it runs in,
+// checked by both engines before any set-up. The sweeps run in the Arnoldi
+// precision on the Arnoldi matrix, so the preconditioner precision has to be
+// that precision (not mode single-prec) and the matrix has to exist in it
+// (not mode mixed-half, whose inner operator is the fp16 copy).
+inline void check_neumann_args(const mpg_solve_args& a) {
+    if (a.jacobi_steps < 1 || a.jacobi_steps > 64)
+        throw std::invalid_argument("prec neumann: jacobi_steps = " + std::to_string(a.jacobi_steps) +
+                                    " is outside [1, 64]");
+    if (a.mode == MPG_MODE_SINGLE_PREC)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          "prec neumann is not available in mode single-prec: the sweeps run in the Arnoldi "
+                          "precision and would need A in a second precision");
+    if (a.mode == MPG_MODE_MIXED_HALF)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          "prec neumann is not available in mode mixed-half: the inner operator is the fp16 copy of A");
+}
 
 // Communication seam of the row-partitioned solve: a single-GPU engine has
 // no communicator; a multi-GPU rank supplies one (see comm.hpp).
@@ -126,6 +145,7 @@ public:
     // mpg_csr_half_values, capi.h; zeros in other modes)
     const int64_t* half_stats() const;
     int prec_fused() const;  // mpg_engine_prec_fused
+    int prec_sweeps() const;  // mpg_engine_prec_sweeps
     int step_dots_steps() const;       // steps of a cycle that run the SpMV inside the dots' launch
     void sync();
     const CyclePolicy& policy() const;  // mpg_engine_cycle_policy

@@ -12,7 +12,9 @@
 // mpg_gen_spec), --mode mixed-half, --half-unscaled (mixed-half: plain fp16
 // cast, a value outside fp16's range is an error), --engine {fused,surface},
 // --prec bjacobi [--prec-block {2,3,4}] (the inverse of each node's diagonal
-// block; 3 unknowns per node unless told), --device D, --stop-on-breakdown (end the solve with an error at the first
+// block; 3 unknowns per node unless told), --prec neumann [--jacobi-steps S]
+// (S Jacobi sweeps on A z = r from z = 0, the truncated Neumann series;
+// 1 <= S <= 64, S = 1 is --prec jacobi), --device D, --stop-on-breakdown (end the solve with an error at the first
 // non-finite Arnoldi residual; without it the count goes to stderr),
 // --ngpus N (row-partition the fused solve over N GPUs of this process, one
 // host thread per GPU, RCCL clique by ncclCommInitAll: mpg_solve_multi_gpu;
@@ -109,6 +111,7 @@ int main(int argc, char* argv[]) {
             else if (v == "jacobi") a.prec = MPG_PREC_JACOBI;
             else if (v == "ilu_jacobi") a.prec = MPG_PREC_ILU_JACOBI;
             else if (v == "bjacobi") a.prec = MPG_PREC_BLOCK_JACOBI;
+            else if (v == "neumann") a.prec = MPG_PREC_NEUMANN;
             else { std::cout << "Unknown Preconditioner" << std::endl; return 1; }
         } else if (f == "--engine") {
             const std::string v = next();

@@ -183,4 +183,41 @@ public:
     void apply(Vect<Type, Device> rhs) override { bjacobi_apply(bs_, dinv_, rhs); }
 };
 
+// backend primitive: one Jacobi sweep z_out = z_in + dinv * (r - A z_in) on
+// a square A, the three epilogue operations each rounded to Type; z_out may
+// be r, never z_in
+template <class Type, class Device>
+void jacobi_sweep(SparseMatrix<Type, Device> A, Vect<Type, Device> dinv, Vect<Type, Device> r,
+                  Vect<Type, Device> z_in, Vect<Type, Device> z_out);
+
+// Jacobi-sweep polynomial preconditioner (an addition to the reference's
+// set): `steps` Jacobi sweeps on A z = r from z = 0, the truncated Neumann
+// series M^-1 = sum_{j<steps} (I - D A)^j D. D is Jacobi's inverse diagonal
+// of A_diag (the matrix Jacobi is built from); the sweeps run on A, the
+// matrix the Arnoldi cycle runs on. steps = 1 is Jacobi's apply.
+template <class Type, class Device>
+class Neumann : public LinearOperator<Type, Device> {
+    SparseMatrix<Type, Device> A_;
+    int steps_;
+    Vect<Type, Device> diag_, work0_, work1_;
+
+public:
+    Neumann(SparseMatrix<Type, Device> A_diag, SparseMatrix<Type, Device> A, int steps)
+        : A_(A), steps_(steps), diag_(A.nrows()) {
+        jacobi_diag(A_diag, diag_);
+        if (steps >= 2) work0_ = Vect<Type, Device>(A.nrows());
+        if (steps >= 3) work1_ = Vect<Type, Device>(A.nrows());
+    }
+    int n() const { return (int)diag_.n(); }
+    int steps() const { return steps_; }
+    Vect<Type, Device> diag_vect() { return diag_; }
+    // z_1 = D rhs (in place for one step), then the sweeps between the work
+    // vectors with rhs as r; the last one stores into rhs
+    void apply(Vect<Type, Device> rhs) override {
+        gdmv(1.0, diag_, rhs, 0.0, steps_ == 1 ? rhs : work0_);
+        for (int j = 1; j < steps_; ++j)
+            jacobi_sweep(A_, diag_, rhs, (j - 1) & 1 ? work1_ : work0_, j == steps_ - 1 ? rhs : (j & 1 ? work1_ : work0_));
+    }
+};
+
 #endif  // MPGMRES_KERNELS_HPP

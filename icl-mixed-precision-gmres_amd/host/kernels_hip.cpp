@@ -1147,6 +1147,26 @@ template <> void bjacobi_apply<float, Hip>(int bs, Vect<float, Hip> d, Vect<floa
     assert(d.n() == x.n() * (size_t)bs);
     check(mpg_bjacobi_apply_f32(C, (int64_t)x.n(), bs, d.data(), x.data()), "block Jacobi apply");
 }
+// one Jacobi sweep, on the SELL copy where spmv would run on one, else on
+// the CSR arrays (a node-block copy keeps them: the same row sums)
+template <> void jacobi_sweep<double, Hip>(SparseMatrix<double, Hip> A, Vect<double, Hip> d, Vect<double, Hip> r,
+                                           Vect<double, Hip> zi, Vect<double, Hip> zo) {
+    assert(A.nrows() == A.ncols() && !A.is_transposed() && (size_t)A.nrows() == r.n() && d.n() == r.n() &&
+           zi.n() == r.n() && zo.n() == r.n());
+    mpg_sell_t s = A.node() ? nullptr : A.sell();
+    check(s ? mpg_sell_jacobi_sweep_f64(C, s, d.data(), r.data(), zi.data(), zo.data())
+            : mpg_csr_jacobi_sweep_f64(C, A.csr(), A.vals_data(), d.data(), r.data(), zi.data(), zo.data()),
+          "Jacobi sweep");
+}
+template <> void jacobi_sweep<float, Hip>(SparseMatrix<float, Hip> A, Vect<float, Hip> d, Vect<float, Hip> r,
+                                          Vect<float, Hip> zi, Vect<float, Hip> zo) {
+    assert(A.nrows() == A.ncols() && !A.is_transposed() && (size_t)A.nrows() == r.n() && d.n() == r.n() &&
+           zi.n() == r.n() && zo.n() == r.n());
+    mpg_sell_t s = A.node() ? nullptr : A.sell();
+    check(s ? mpg_sell_jacobi_sweep_f32(C, s, d.data(), r.data(), zi.data(), zo.data())
+            : mpg_csr_jacobi_sweep_f32(C, A.csr(), A.vals_data(), d.data(), r.data(), zi.data(), zo.data()),
+          "Jacobi sweep");
+}
 
 // ---- ILU(0) / ILU-Jacobi (kernels_mkl.cpp:355-506, kernels_cuda.cpp:617-791) ----
 namespace {

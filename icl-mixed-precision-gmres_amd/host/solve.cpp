@@ -9,6 +9,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "IterUtil.hpp"
 #include "Orthogonalization.hpp"
@@ -42,11 +43,19 @@ std::unique_ptr<Convergence<T, Hip>> make_convergence(const mpg_solve_args& a) {
 }
 
 // gmres_perf_test.cpp:69-89, 139-159 (ILU from the fp64 A; Jacobi from A
-// converted to the preconditioner precision)
+// converted to the preconditioner precision). inner: the matrix the Arnoldi
+// cycle runs on when it is held in P (prec neumann sweeps on it), else nullptr.
 template <class P>
 std::unique_ptr<LinearOperator<P, Hip>> make_preconditioner(int prec, const SparseMatrix<double, Hip>& A,
-                                                            int jacobi_steps, int prec_block) {
+                                                            int jacobi_steps, int prec_block,
+                                                            const SparseMatrix<P, Hip>* inner) {
     switch (prec) {
+        case MPG_PREC_NEUMANN: {
+            if (!inner)
+                throw StatusError(MPG_ERR_UNSUPPORTED, "prec neumann needs the Arnoldi matrix in the preconditioner "
+                                                       "precision");
+            return std::make_unique<Neumann<P, Hip>>(SparseMatrix<P, Hip>(A), *inner, jacobi_steps);
+        }
         case MPG_PREC_BLOCK_JACOBI: {
             const int bs = prec_block == 0 ? 3 : prec_block;
             if (bs < 2 || bs > 4) throw std::invalid_argument("prec bjacobi: prec_block must be 2, 3 or 4 (0: 3)");
@@ -120,7 +129,9 @@ void do_baseline(const mpg_solve_args& a, const SparseMatrix<double, Hip>& A, Ve
     // fp32-rounded copy, widened back for Type = double.
     const SparseMatrix<float, Hip> A_f32(A);
     const SparseMatrix<Type, Hip> A_type(A_f32);
-    auto M = make_preconditioner<PrecType>(a.prec, A, a.jacobi_steps, a.prec_block);
+    const SparseMatrix<PrecType, Hip>* inner = nullptr;
+    if constexpr (std::is_same_v<Type, PrecType>) inner = &A_type;
+    auto M = make_preconditioner<PrecType>(a.prec, A, a.jacobi_steps, a.prec_block, inner);
     Hip::fence();
     const double prec_s = seconds_since(t0);
 
@@ -153,7 +164,7 @@ void do_mixed(const mpg_solve_args& a, const SparseMatrix<double, Hip>& A, Vect<
     Vect<double, Hip> x(n);
     auto t0 = clk::now();
     const SparseMatrix<float, Hip> A_single(A);
-    auto M = make_preconditioner<float>(a.prec, A, a.jacobi_steps, a.prec_block);
+    auto M = make_preconditioner<float>(a.prec, A, a.jacobi_steps, a.prec_block, &A_single);
     Hip::fence();
     const double prec_s = seconds_since(t0);
 
@@ -186,6 +197,7 @@ void dispatch_mode(const mpg_solve_args& a, const SparseMatrix<double, Hip>& A, 
 }  // namespace
 
 int solve_surface(const mpg_solve_args& a, mpg_solve_result* r) {
+    if (a.prec == MPG_PREC_NEUMANN) check_neumann_args(a);
     SparseMatrix<double, Hip> A(a.n, a.n, a.rowptr, a.col, a.val);
     const size_t n = (size_t)a.n;
     Vect<double, Hip> b(n), xt(n);

@@ -59,7 +59,8 @@ typedef struct {
     mpg_csr_t A;           /* analysed local CSR, columns in [-n_front, n_ext) */
     const void* val_outer; /* residual values, outer_type */
     const void* val_inner; /* Arnoldi values, inner_val */
-    const void* diag;      /* Jacobi inverse diagonal (prec_type) or NULL */
+    const void* diag;      /* Jacobi inverse diagonal (prec_type) or NULL; with jacobi == 0 the phase
+                              kernels do not read it (mpg_arnoldi_neumann_apply does) */
     const void* b;         /* outer_type, n */
     void* x;               /* outer_type, row 0 of [-MPG_FRONT_PAD(n_front), n_ext) (halo filled by the caller) */
     int32_t spmv_format;   /* Arnoldi SpMV storage: 0 auto, 1 CSR row blocks, 2 sliced ELL (SELL-64),
@@ -88,6 +89,23 @@ int mpg_arnoldi_destroy(mpg_arnoldi_t a);
  * residual prologue) apply the block inverses themselves -- node-block storage, 3 x 3 blocks -- with
  * the bits of mpg_bjacobi_apply_* on their output; 0 when the caller has to apply them */
 int mpg_arnoldi_prec_fused(mpg_arnoldi_t a, int which);
+/* The Jacobi-sweep polynomial preconditioner (MPG_PREC_NEUMANN, solve.h) on the
+ * workspace's own Arnoldi matrix: w <- sum_{j<steps} (I - D A)^j D w, with D =
+ * desc.diag (kept by the workspace also when desc.jacobi == 0, which is how
+ * this preconditioner is set up: the phase kernels then apply none) and A the
+ * inner values on the storage the Arnoldi SpMV runs (the SELL copy, else the
+ * CSR arrays: a node-block workspace sweeps its CSR arrays, the same bits).
+ * mpg_gdmv_*(1, D, w, 0, .) forms z_1 (in place for steps == 1: point
+ * Jacobi's bits), then steps - 1 sweeps of mpg_*_jacobi_sweep_*'s arithmetic
+ * (capi.h) in the workspace's accumulation class run between work0 and work1
+ * with w as r; the last one stores into w. w, work0, work1: n entries of T,
+ * distinct; work1 may be NULL for steps <= 2, work0 for steps == 1. work0
+ * holds finite values on entry (gdmv forms 0 * work0 + D w; mpg_malloc
+ * zero-fills, and every application leaves finite values there). Launches
+ * only (capturable). MPG_ERR_ARG: steps outside [1, 64], a missing vector or
+ * diagonal; MPG_ERR_UNSUPPORTED: a preconditioner precision or value type
+ * other than T (single-prec, mixed-half), or a workspace with halo rows. */
+int mpg_arnoldi_neumann_apply(mpg_arnoldi_t a, int32_t steps, void* w, void* work0, void* work1);
 
 /* Storage the Arnoldi SpMV runs on: *format 1 = CSR row blocks (cuSPARSE
  * csrmv's input, types_cuda.hpp:53-60), 2 = SELL-64 copy made at create

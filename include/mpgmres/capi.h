@@ -455,6 +455,27 @@ int mpg_bjacobi_apply_f64(mpg_ctx_t ctx, int64_t n, int32_t bs, const double* di
 int mpg_bjacobi_apply_f32(mpg_ctx_t ctx, int64_t n, int32_t bs, const float* dinv, float* x);
 int mpg_bjacobi_apply_f64_p32(mpg_ctx_t ctx, int64_t n, int32_t bs, const float* dinv, double* x);
 
+/* ---- Jacobi sweep (neumann.hip): one sweep of z <- z + D (r - A z) on a
+ * square matrix, the step of the truncated Neumann series
+ * M^-1 = sum_{j<s} (I - D A)^j D (z_1 = D r is mpg_gdmv_*(1, dinv, r, 0, z)).
+ * Per row i, in the vectors' type T:
+ *   s_i = T(sum_j a_ij z_in[j])   the row sum of mpg_csr_spmv_* / mpg_sell_spmv_*
+ *                                 at alpha = 1, beta = 0 (fp64 sums, CSR order)
+ *   t = r[i] - s_i;  u = dinv[i] * t;  z_out[i] = z_in[i] + u
+ * each of the three rounded to T (no contraction). dinv: the inverse diagonal
+ * of mpg_jacobi_setup_* / mpg_jacobi_diag_*. z_out may be r itself (row i's
+ * lane alone reads r[i], before its store); z_out == z_in is MPG_ERR_ARG
+ * (other rows gather z_in). One launch; MPG_ERR_ARG for a non-square matrix,
+ * a NULL argument or a copy of another value type. */
+int mpg_csr_jacobi_sweep_f64(mpg_ctx_t ctx, mpg_csr_t A, const double* vals, const double* dinv, const double* r,
+                             const double* z_in, double* z_out);
+int mpg_csr_jacobi_sweep_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, const float* dinv, const float* r,
+                             const float* z_in, float* z_out);
+int mpg_sell_jacobi_sweep_f64(mpg_ctx_t ctx, mpg_sell_t A, const double* dinv, const double* r, const double* z_in,
+                              double* z_out);
+int mpg_sell_jacobi_sweep_f32(mpg_ctx_t ctx, mpg_sell_t A, const float* dinv, const float* r, const float* z_in,
+                              float* z_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,10 @@ typedef enum {
     MPG_PREC_ILU_JACOBI = 1,
     MPG_PREC_JACOBI = 2,
     MPG_PREC_IDENTITY = 3,
-    MPG_PREC_BLOCK_JACOBI = 4 /* new: the inverse of each node's diagonal block (mpg_bjacobi_*, capi.h) */
+    MPG_PREC_BLOCK_JACOBI = 4, /* new: the inverse of each node's diagonal block (mpg_bjacobi_*, capi.h) */
+    MPG_PREC_NEUMANN = 5 /* new: jacobi_steps Jacobi sweeps on A z = r from z = 0, the truncated Neumann series
+                            sum_{j<s} (I - D A)^j D with Jacobi's D (mpg_*_jacobi_sweep_*, capi.h); s = 1 is
+                            MPG_PREC_JACOBI's bits */
 } mpg_prec_t;
 
 typedef enum {
@@ -63,7 +66,8 @@ typedef struct {
     double rtol;           /* --rtol (0: base Convergence) */
     int32_t repeat_iter;   /* --repeat-iter */
     int32_t orthloss;      /* --orthloss */
-    int32_t jacobi_steps;  /* --jacobi-steps */
+    int32_t jacobi_steps;  /* --jacobi-steps: sweeps of MPG_PREC_ILU_JACOBI's solves; MPG_PREC_NEUMANN's sweep
+                              count s, 1 <= s <= 64 (anything else MPG_ERR_ARG) */
     int32_t verbose;       /* print the reference's stdout lines */
     int32_t device;        /* HIP device (mpg_solve only) */
     int32_t threads;       /* host threads (oracle only; 0 = default) */
@@ -195,6 +199,9 @@ int mpg_engine_step_dots_status(mpg_engine_t e, int k);
 /* block Jacobi: 1 when the apply runs inside the SpMV / residual launches, 0 when it is a
  * launch of its own between them and the dots; -1 for every other preconditioner */
 int mpg_engine_prec_fused(mpg_engine_t e);
+/* MPG_PREC_NEUMANN: the sweep count the engine applies per preconditioner application (jacobi_steps:
+ * one gdmv launch and that many minus one sweep launches); -1 for every other preconditioner */
+int mpg_engine_prec_sweeps(mpg_engine_t e);
 /* the accumulation class the engine's Arnoldi runs: MPG_ACCUM_F64 0 / MPG_ACCUM_F32 1 (arnoldi.h) */
 int mpg_engine_accum(mpg_engine_t e);
 /* the residual prologue's storage (mpg_arnoldi_prologue_format: 1 CSR, 2 SELL, 3 node blocks) */
@@ -228,7 +235,8 @@ typedef struct {
     int32_t fuse_dots, fuse_dots_required, fuse_dots_k0; /* MPG_FUSE_DOTS (= 2: required), MPG_FUSE_DOTS_K0 */
     int32_t step_dots;    /* MPG_STEP_DOTS: 0 never, 1 wherever supported, 2 required, -1 the steps lo <= k + 1 <= hi */
     int32_t step_dots_lo, step_dots_hi;
-    int32_t sep_prec;          /* a preconditioner that is not applied inside the phase kernels (ILU, block Jacobi) */
+    int32_t sep_prec;          /* a preconditioner that is not applied inside the phase kernels (ILU, block Jacobi,
+                                  the Jacobi-sweep polynomial) */
     int32_t sep_prec_step;     /* ... a launch of its own after every SpMV */
     int32_t sep_prec_prologue; /* ... and after the residual prologue */
     int32_t partials_max_cols; /* mpg_arnoldi_partials_max_cols() */
