@@ -148,6 +148,7 @@ class RankLayout(C.Structure):
         ("half_rows_scaled", C.c_int64),
         ("device", C.c_int32),
         ("transport_ranks", C.c_int32),
+        ("cgs_stream", C.c_int32),
     ]
 
 

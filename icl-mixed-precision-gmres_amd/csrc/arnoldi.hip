@@ -142,6 +142,9 @@ int mpg_arnoldi_create(mpg_ctx_t ctx, const mpg_arnoldi_desc* desc, mpg_arnoldi_
     a->d = *desc;
     a->combo = combo;
     a->tsize = desc->vec_type == MPG_F64 ? 8 : 4;
+    // read once: every launch of this workspace, captured or not, and
+    // mpg_arnoldi_cgs_stream_at then go by the same setting
+    if (const char* e = std::getenv("MPG_CGS_PREFETCH"); e && (*e == '0' || *e == '1')) a->cgs_pref = *e - '0';
     a->G = desc->A->nblocks < kGroups ? (desc->A->nblocks > 0 ? desc->A->nblocks : 1) : kGroups;
     a->Grb = desc->A->nblocks > 0 ? desc->A->nblocks : 1;
     a->Gd = (int)std::min<int64_t>(kCombineGroups, std::max<int64_t>(1, ((int64_t)desc->n + 4 * kCombineBlock - 1) /
@@ -378,6 +381,9 @@ int mpg_arnoldi_step_dots(mpg_arnoldi_t a, int k, int fold) {
 }
 int mpg_arnoldi_step_dots_supported(mpg_arnoldi_t a, int k) {
     return a && a->acc32 ? mpg_acc32::step_dots_ok(a, k) : step_dots_check<double>(a, k);
+}
+int mpg_arnoldi_cgs_stream_at(mpg_arnoldi_t a, int k) {
+    return a && a->acc32 ? mpg_acc32::cgs_stream_at(a, k) : cgs_stream_check<double>(a, k);
 }
 int mpg_arnoldi_givens_spmv(mpg_arnoldi_t a, int k) { return spmv_impl(a, k, 1); }
 int mpg_arnoldi_givens_partials_spmv(mpg_arnoldi_t a, int k) { return spmv_impl(a, k, 2); }

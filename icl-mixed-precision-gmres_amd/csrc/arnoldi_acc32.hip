@@ -10,6 +10,7 @@ int spmv(mpg_arnoldi* a, int k, int fold, bool dots) { return spmv_run<float>(a,
 int step_dots(mpg_arnoldi* a, int k, int fold) { return step_dots_run<float>(a, k, fold); }
 int step_dots_ok(const mpg_arnoldi* a, int k) { return step_dots_check<float>(a, k); }
 int spmv_dots_ok(const mpg_arnoldi* a, int k) { return spmv_dots_check<float>(a, k); }
+int cgs_stream_at(const mpg_arnoldi* a, int k) { return cgs_stream_check<float>(a, k); }
 int dots(mpg_arnoldi* a, int k, bool combine) { return dots_run<float>(a, k, combine); }
 int cgs(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool no_next) {
     return cgs_run<float>(a, k, pass, givens, from_partials, no_next);

@@ -1533,6 +1533,71 @@ __global__ __launch_bounds__(BS) void k_dots_panels(int n, const T* __restrict__
     else dots_panel<T, BS, NCL, A>(n, V + (int64_t)c0 * ld, ld, w, part);
 }
 
+// ---- pieces of the streaming CGS update (k_cgs_update_nc<..., STREAM>) ----
+// Beside an LDS-DMA in flight the compiler waits vmcnt(0) at the first use of
+// any load it counts and before every ds_read that may see a DMA's bytes, so
+// the three accesses that must not drain the ring are kept out of its count:
+// the partial loads, and the reads of a slot and of a coefficient. Each is
+// paired with its own wait, stated where it is issued.
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+constexpr int kStreamSlots = 9;  // 16 KB each for 1024 lanes: 144 KB of the CU's 160 KB
+
+// one partial, requested and not waited for (cgs_stream_wait_partials does).
+// ASSUMPTION: the returned register is still being filled. The compiler takes
+// it as written when the statement ends, and nothing but its one use -- the
+// "+v" operand of cgs_stream_wait_partials -- orders a reader behind the
+// load: the value must reach that statement in the register the load names,
+// with no copy, spill or coalescing move between the two. The 8 values have
+// no other use and are requested at the kernel's entry, far from any register
+// pressure, and in the gfx950 code of every instance built the registers are
+// untouched from the load to the wait; after a compiler change check that
+// again (tools/kernel_resources.py for spills, the assembly between the
+// global_load_dwordx2 group and the first s_waitcnt vmcnt for a v_mov).
+__device__ __forceinline__ double cgs_stream_load_partial(const double* p) {
+    double v;
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+    return v;
+}
+// the 8 partials have landed once at most BEHIND younger requests are pending
+template <int BEHIND>
+__device__ __forceinline__ void cgs_stream_wait_partials(double (&p)[8]) {
+    asm volatile("s_waitcnt vmcnt(%8)"
+                 : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7])
+                 : "i"(BEHIND)
+                 : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+// the lane's 16 bytes of a slot and one coefficient, once at most BEHIND
+// requests younger than the slot's own are pending; on return both reads have
+// completed, so the slot may be requested again
+template <int BEHIND>
+__device__ __forceinline__ void cgs_stream_take(unsigned slot_lds, unsigned coef_lds, f32x4_t& v, float& cu) {
+    asm volatile("s_waitcnt vmcnt(%4)\n\tds_read_b128 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v), "=&v"(cu)
+                 : "v"(slot_lds), "v"(coef_lds), "i"(BEHIND)
+                 : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+// the lane's 16 bytes of a column, global -> LDS with no register between:
+// one wave-instruction writes 1 KB at the wave-uniform `lds_wave` + lane * 16
+__device__ __forceinline__ void cgs_stream_request(const float* g, unsigned lds_wave) {
+    __builtin_amdgcn_global_load_lds(g, (lds_ptr_t)(size_t)lds_wave, 16, 0, 0);
+}
+// the sums so far are formed here (an empty statement the compiler cannot
+// move the products across)
+__device__ __forceinline__ void cgs_stream_pin(float (&t)[4]) {
+    asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+}
+// f(integral_constant<int, C>) for C = 0 .. N - 1, in order
+template <int C, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (C < N) {
+        f(std::integral_constant<int, C>{});
+        static_for<C + 1, N>(f);
+    }
+}
+
 // coef = T(sums[0..NC)); w = w - T(V coef); partial ||w'||^2 (the last
 // CGS pass; same arithmetic and order as k_cgs_update).
 // FROM_PARTS (one GPU): the coefficients are summed here from the one-panel
@@ -1547,8 +1612,17 @@ __global__ __launch_bounds__(BS) void k_dots_panels(int n, const T* __restrict__
 // behind the partial loads, so its memory latency runs under the coefficient
 // sums; the coefficients are published with an LDS-only barrier
 // (__syncthreads would drain those loads). Same operands, same order.
+// STREAM (with FROM_PARTS, fp32 basis and class): the lane's first row group
+// streams its basis columns through a ring of LDS slots (cgs_stream_*,
+// above): w and the first kStreamSlots columns are requested right behind
+// the partial loads, a slot is refilled with column c + R as soon as column
+// c has been read out of it, and each column is retired by a counted vmcnt,
+// so the lane keeps R columns in flight until the last one is requested.
+// The partials are loaded outside the compiler's wait bookkeeping (it would
+// wait vmcnt(0) at their first use and drain the ring). Same operands, the
+// columns added in the same ascending order.
 template <class T, int BS, int NC, bool FROM_PARTS = false, bool NEXT_DOTS = false, bool PF = false,
-          bool STAMP = false, class A = double>
+          bool STAMP = false, class A = double, bool STREAM = false>
 __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict__ V, int64_t ld,
                                                       const double* __restrict__ sums, int part_G,
                                                       T* __restrict__ coef_out, T* __restrict__ w,
@@ -1558,25 +1632,64 @@ __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict
     static_assert(!FROM_PARTS || BS >= 32 * NC, "32 lanes per column");
     static_assert(!PF || (FROM_PARTS && !NEXT_DOTS), "prefetch under the partial sums");
     static_assert(!PF || NC <= kColBatch<T>, "the prefetch form holds one batch of columns (the only form run)");
+    static_assert(!STREAM || (FROM_PARTS && !NEXT_DOTS && !PF && !STAMP && sizeof(T) == 4 && sizeof(A) == 4),
+                  "the streaming form: the last pass with in-launch sums, fp32 basis, fp32 class");
     constexpr int B = kColBatch<T>;
     constexpr int B0 = NC < B ? NC : B;
+    constexpr int R = NC < kStreamSlots ? NC : kStreamSlots;  // the ring's depth
     __shared__ A coef[NC];
     const int n4 = n & ~3;
     const int i_first = 4 * (blockIdx.x * BS + threadIdx.x);
     Raw4<T> pw, pv[PF ? B0 : 1];
+    // clamped row of the early requests: every lane reads valid memory
+    const int ip = i_first < n4 ? i_first : 0;
+    unsigned ring_lane = 0;  // LDS byte address of this lane's 16 bytes of slot 0
     if constexpr (FROM_PARTS) {
         const int j = threadIdx.x / 32, sub = threadIdx.x % 32;
         const int jc = j < NC ? j : NC - 1;
         constexpr int Q = kCombineGroups / 32;
         A pp[Q];
+        if constexpr (STREAM) {
+            static_assert(Q == 8, "cgs_stream_wait_partials names 8 loads");
+            double pd[Q];
 #pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int g = sub + 32 * q;
-            pp[q] = (A)sums[(size_t)jc * part_G + (g < part_G ? g : 0)];
+            for (int q = 0; q < Q; ++q) {
+                const int g = sub + 32 * q;
+                pd[q] = cgs_stream_load_partial(sums + (size_t)jc * part_G + (g < part_G ? g : 0));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            pw.load(w + ip);
+            __builtin_amdgcn_sched_barrier(0);  // w is older than every column: the counts below say so
+            // The image of one slot: lane t's row quad of the slot's column at
+            // byte 16 t, which is what one LDS-DMA wave-instruction writes
+            // (wave-uniform base + lane * 16 B) when the base is the slot's
+            // address of the wave's first lane. A lane only ever reads the 16
+            // bytes it requested itself, so no lane waits for another lane's
+            // request: the lane's own counted vmcnt orders its read, and the
+            // read's lgkmcnt(0) orders the slot's refill. No barrier.
+            __shared__ float4 ring[R][BS];
+            static_assert(sizeof(float4) == 16 && sizeof(ring[0]) == 16 * BS && BS % kWave == 0 &&
+                              sizeof(ring) + sizeof(coef) + 64 <= 160 * 1024,
+                          "lane-linear 16-B image, whole waves, inside the CU's LDS");
+            const int wave0 = wave_id() * kWave;
+            ring_lane = (unsigned)(size_t)(lds_ptr_t)&ring[0][threadIdx.x];
+            const unsigned ring_wave0 = (unsigned)(size_t)(lds_ptr_t)&ring[0][wave0];
+#pragma unroll
+            for (int u = 0; u < R; ++u) cgs_stream_request(V + (int64_t)u * ld + ip, ring_wave0 + u * 16 * BS);
+            __builtin_amdgcn_sched_barrier(0);
+            // the partials are the oldest requests: w and R columns stay in flight
+            cgs_stream_wait_partials<1 + R>(pd);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) pp[q] = (A)pd[q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const int g = sub + 32 * q;
+                pp[q] = (A)sums[(size_t)jc * part_G + (g < part_G ? g : 0)];
+            }
         }
         if constexpr (PF) {
             __builtin_amdgcn_sched_barrier(0);
-            const int ip = i_first < n4 ? i_first : 0;
             pw.load(w + ip);
 #pragma unroll
             for (int u = 0; u < B0; ++u) pv[u].load(V + (int64_t)u * ld + ip);
@@ -1598,14 +1711,55 @@ __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict
         coef[threadIdx.x] = (A)c;
         if (blockIdx.x == 0) coef_out[threadIdx.x] = c;
     }
-    if constexpr (PF) lds_barrier();
+    if constexpr (PF || STREAM) lds_barrier();  // (__syncthreads would drain the requests in flight)
     else __syncthreads();
     constexpr int NA = NEXT_DOTS ? Pow2Ceil<NC>::v : 1;
     A acc[NA];
 #pragma unroll
     for (int c = 0; c < NA; ++c) acc[c] = A(0);
+    // w' = w - T(t) for one row quad, and its share of ||w'||^2
+    auto finish_rows = [&](int i, const A (&t)[4], const Raw4<T>& wr, A (&wd)[4]) {
+        T wo[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            wo[r] = T(-1) * (T)t[r] + T(1) * (T)wr[r];
+            wd[r] = (A)wo[r];
+            if (!NEXT_DOTS) acc[0] += wd[r] * wd[r];
+        }
+        Row4<T>::store(w + i, wo);
+    };
+    int i_loop = i_first;
+    if constexpr (STREAM) {
+        // every lane runs the ring to its end, so no request outlives the
+        // workgroup's LDS; lanes past the last row quad store nothing
+        A t[4] = {A(0), A(0), A(0), A(0)};
+        const unsigned coef_lds = (unsigned)(size_t)(lds_ptr_t)&coef[0];
+        const unsigned ring_wave = __builtin_amdgcn_readfirstlane(ring_lane);
+        static_for<0, NC>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            constexpr unsigned slot = (unsigned)((c % R) * 16 * BS);
+            // columns c + 1 .. c + R - 1 were requested after column c
+            constexpr int behind = NC - 1 - c < R - 1 ? NC - 1 - c : R - 1;
+            f32x4_t x;
+            A cu;
+            cgs_stream_take<behind>(ring_lane + slot, coef_lds + 4u * c, x, cu);
+            if constexpr (c + R < NC) cgs_stream_request(V + (int64_t)(c + R) * ld + ip, ring_wave + slot);
+            Raw4<T> v;
+            v.v = make_float4(x.x, x.y, x.z, x.w);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) t[r] += v.template at<A>(r) * cu;
+            // the products are formed here: left to the compiler they sink
+            // into the row test below, and every column read stays live (spills)
+            cgs_stream_pin(t);
+        });
+        if (i_first < n4) {
+            A wd[4];
+            finish_rows(i_first, t, pw, wd);
+        }
+        i_loop = i_first + 4 * gridDim.x * BS;
+    }
     bool first = PF;
-    for (int i = i_first; i < n4; i += 4 * gridDim.x * BS) {
+    for (int i = i_loop; i < n4; i += 4 * gridDim.x * BS) {
         Raw4<T> wr;
         if (first) wr = pw;
         else wr.load(w + i);
@@ -1628,15 +1782,8 @@ __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict
                     for (int r = 0; r < 4; ++r) t[r] += v[u].template at<A>(r) * cu;
                 }
         }
-        T wo[4];
         A wd[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            wo[r] = T(-1) * (T)t[r] + T(1) * (T)wr[r];
-            wd[r] = (A)wo[r];
-            if (!NEXT_DOTS) acc[0] += wd[r] * wd[r];
-        }
-        Row4<T>::store(w + i, wo);
+        finish_rows(i, t, wr, wd);
         first = false;
         if constexpr (NEXT_DOTS) {
 #pragma unroll
@@ -2208,6 +2355,7 @@ struct mpg_arnoldi {
     double* report = nullptr;   // 4 + m
     unsigned* counters = nullptr;  // last-arriver tickets: [0] dots, [32] CGS + Givens (zeroed at create)
     int Gd = 1;                    // workgroups (kCombineBlock threads) of the combining panel dots
+    int cgs_pref = -1;             // MPG_CGS_PREFETCH as read at create: 0 / 1, -1 unset (the CGS update's form)
     SellCopy sell;  // sliced-ELL copy of the Arnoldi matrix (nslices == 0: CSR row blocks)
     SellCopy sell_outer;        // ... of the outer-precision values, for the residual prologue
     NodeCopy node;              // node-block copy of the Arnoldi matrix (nblk > 0: the Arnoldi SpMV uses it)

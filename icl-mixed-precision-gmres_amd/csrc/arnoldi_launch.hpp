@@ -362,11 +362,59 @@ int dots_run(mpg_arnoldi_t a, int k, bool combine) {
 // 26.92k against 26.75k it/s, the update 11.98 against 12.27 us;
 // profiles/r06_pf/), off in the fp64 class (round 4: no gain).
 // MPG_CGS_PREFETCH=0 / 1 forces it.
+// (read when the workspace is created: mpg_arnoldi::cgs_pref)
 template <class A>
-inline bool cgs_prefetch() {
-    const char* e = std::getenv("MPG_CGS_PREFETCH");
-    if (e && (*e == '0' || *e == '1')) return *e == '1';
+inline bool cgs_prefetch(const mpg_arnoldi* a) {
+    if (a->cgs_pref >= 0) return a->cgs_pref == 1;
     return std::is_same_v<A, float>;
+}
+
+// The form of the in-launch-sum CGS update at nc columns: kCgsPlain (the
+// product form: the bit tests' reference, and the one the wave stamps time),
+// kCgsPrefetch (PF, nc <= one batch) or kCgsStream (k_cgs_update_nc<...,
+// STREAM>: the columns through a ring of LDS slots, requested under the
+// coefficient sums and refilled as they are consumed; built for an fp32 basis
+// in the fp32 accumulation class, every nc <= kNC). MPG_CGS_PREFETCH=0: plain
+// everywhere; =1: the streaming form wherever it is built, else PF where that
+// is; unset: kCgsStreamFrom and above stream, PF below it (fp32 class), and
+// the fp64 class runs what it ran before the streaming form existed (plain).
+// The multi-rank engine takes the same form: its partials are all-reduced in
+// place ahead of this launch, which then sums them itself exactly as on one
+// GPU (FROM_PARTS), so the same requests hide under the same sums
+// (tests/test_cgs_stream_gpu.py::test_two_ranks_same_bits).
+// A launch with an armed wave stamp (a timer's, never the solve's) runs the
+// stamped plain form whatever this says.
+enum { kCgsPlain = 0, kCgsPrefetch = 1, kCgsStream = 2 };
+constexpr int kCgsStreamFrom = 9;  // (NC <= 8: PF measured 0 - 0.4 us per launch below the ring; profiles/r11_cgs_stream/)
+template <class T, class A>
+inline int cgs_update_form(const mpg_arnoldi* a, int nc) {
+    if (!cgs_prefetch<A>(a)) return kCgsPlain;
+    constexpr bool built = std::is_same_v<T, float> && std::is_same_v<A, float>;
+    const bool forced = a->cgs_pref == 1;
+    if (built && nc <= kNC && (forced || nc >= kCgsStreamFrom)) return kCgsStream;
+    return nc <= kColBatch<T> ? kCgsPrefetch : kCgsPlain;
+}
+
+// The streaming form's launch (fp32 basis, fp32 class): the one place that
+// names the instance, whatever type combination's dispatch reaches it.
+template <int NC>
+void cgs_stream_launch(mpg_arnoldi_t a, const float* V, const double* src, int part_G, float* coef_out, float* w) {
+    k_cgs_update_nc<float, kCombineBlock, NC, true, false, false, false, float, true>
+        <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, V, a->ld, src, part_G, coef_out, w, a->partial, nullptr);
+}
+
+// 1 when mpg_arnoldi_cgs_partials(a, k) takes the streaming form, else 0
+// (asked without launching: mpg_arnoldi_cgs_stream_at)
+template <class A>
+int cgs_stream_check(const mpg_arnoldi* a, int k) {
+    if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
+    if (k + 1 > kNC || a->d.orth == kOrthCGSR) return 0;
+    int form = kCgsPlain;
+    dispatch_acc<A>(a->combo, [&](auto t, auto, auto, auto) {
+        form = cgs_update_form<decltype(t), A>(a, k + 1);
+        return (int)MPG_OK;
+    });
+    return form == kCgsStream;
 }
 
 // no_next (CGSR at 32 < k + 1 <= kWideMax, one GPU): a pass that takes its
@@ -426,10 +474,19 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
             // (an armed stamp times the stamped product form, so a measured
             // launch never takes the prefetch variant)
             if (!from_partials) sp = nullptr;
-            const bool pf = from_partials && !sp && cgs_prefetch<A>();
+            const int form = from_partials && !sp ? cgs_update_form<T, A>(a, k + 1) : (int)kCgsPlain;
+            const bool pf = form == kCgsPrefetch;
             return with_nc<kNC>(k + 1, [&](auto nc) {
                 constexpr int NC = decltype(nc)::value;
                 const T* Vp = static_cast<const T*>(a->V);
+                // (NC in the condition: it must depend on this lambda's parameter
+                // for the branch to be discarded where the form is not built)
+                if constexpr (NC >= 1 && std::is_same_v<T, float> && std::is_same_v<A, float>) {
+                    if (form == kCgsStream) {
+                        cgs_stream_launch<NC>(a, Vp, src, part_G, coef_out, w);
+                        return (int)MPG_OK;
+                    }
+                }
                 // (the prefetch variant for one batch of columns only: wider
                 // panels spilled with the prefetched batch held across the sums
                 // in the fp64 class, and in the fp32 class the wider forms
@@ -556,6 +613,7 @@ int reduce(mpg_arnoldi* a, int ncols);
 int spmv(mpg_arnoldi* a, int k, int fold, bool dots);
 int step_dots(mpg_arnoldi* a, int k, int fold);
 int step_dots_ok(const mpg_arnoldi* a, int k);
+int cgs_stream_at(const mpg_arnoldi* a, int k);
 int spmv_dots_ok(const mpg_arnoldi* a, int k);
 int dots(mpg_arnoldi* a, int k, bool combine);
 int cgs(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool no_next);

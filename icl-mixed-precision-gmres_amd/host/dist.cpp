@@ -633,6 +633,7 @@ int solve_rank_threads(const mpg_solve_args* a, int32_t P, mpg_solve_result* r, 
                         L.givens_folded = e.policy().fold;
                         L.device = devices[(size_t)q];
                         L.transport_ranks = comm->transport_ranks();
+                        L.cgs_stream = e.cgs_stream_steps();
                     }
                     const auto t1 = std::chrono::steady_clock::now();
                     bool done = false;

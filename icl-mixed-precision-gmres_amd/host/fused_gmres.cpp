@@ -1007,6 +1007,11 @@ int FusedEngine::prec_sweeps() const { return p_->nm_asked ? p_->nm_asked : -1; 
 int FusedEngine::step_dots_steps() const {
     return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::StepDots; });
 }
+int FusedEngine::cgs_stream_steps() const {
+    return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [&](const Op& o) {
+        return o.kind == OpKind::CgsPartials && mpg_arnoldi_cgs_stream_at(p_->arn, o.a) == 1;
+    });
+}
 const CyclePolicy& FusedEngine::policy() const { return p_->pol; }
 const std::vector<Op>& FusedEngine::cycle_ops() const { return p_->cycle; }
 hipStream_t FusedEngine::stream() const { return p_->stream(); }
@@ -1145,6 +1150,11 @@ int mpg_engine_givens_folded(mpg_engine_t e) {
 int mpg_engine_step_dots_steps(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return e->eng->step_dots_steps();
+}
+
+int mpg_engine_cgs_stream_steps(mpg_engine_t e) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return e->eng->cgs_stream_steps();
 }
 
 int mpg_engine_cycle_policy(mpg_engine_t e, mpg_cycle_policy* out) {

@@ -146,6 +146,7 @@ public:
     const int64_t* half_stats() const;
     int prec_fused() const;  // mpg_engine_prec_fused
     int prec_sweeps() const;  // mpg_engine_prec_sweeps
+    int cgs_stream_steps() const;      // CGS update launches of a cycle that take the streaming form
     int step_dots_steps() const;       // steps of a cycle that run the SpMV inside the dots' launch
     void sync();
     const CyclePolicy& policy() const;  // mpg_engine_cycle_policy

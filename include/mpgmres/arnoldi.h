@@ -203,6 +203,13 @@ int mpg_arnoldi_spmv_dots_supported(mpg_arnoldi_t a, int k);
  * status the launch would, without launching. */
 int mpg_arnoldi_step_dots(mpg_arnoldi_t a, int k, int fold);
 int mpg_arnoldi_step_dots_supported(mpg_arnoldi_t a, int k);
+/* 1 when mpg_arnoldi_cgs_partials(a, k) runs the streaming form of the update
+ * (the lane's basis columns through a ring of LDS slots, requested under the
+ * coefficient sums and refilled as they are consumed: fp32 basis, fp32
+ * accumulation, k + 1 <= 32, plain CGS; MPG_CGS_PREFETCH, as read when the
+ * workspace was created: 0 never, 1 wherever built), else 0; asked without
+ * launching. The same bits either way. */
+int mpg_arnoldi_cgs_stream_at(mpg_arnoldi_t a, int k);
 int mpg_arnoldi_fold_max_m(void);
 /* 1 when folding the Givens step into the SpMV pays at this size (the SpMV's
  * workgroups each sum the partials; past ~4k workgroups a separate Givens

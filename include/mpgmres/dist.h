@@ -121,6 +121,8 @@ typedef struct {
     int64_t half_rows_scaled; /* mixed-half: rows scaled by a power of two */
     int32_t device;           /* the HIP device the rank ran on */
     int32_t transport_ranks;  /* ranks its communicator reports (RCCL: ncclCommCount) */
+    int32_t cgs_stream;       /* CGS update launches per cycle that take the streaming form
+                                 (mpg_engine_cgs_stream_steps) */
 } mpg_rank_layout;
 /* mpg_solve_loopback, reporting each rank's layout (layouts: nranks entries, may be NULL) */
 int mpg_solve_loopback_ex(const mpg_solve_args* args, int32_t nranks, mpg_solve_result* result,

@@ -196,6 +196,9 @@ int mpg_engine_givens_folded(mpg_engine_t e);
  * support check gives at step k (MPG_OK / MPG_ERR_UNSUPPORTED) */
 int mpg_engine_step_dots_steps(mpg_engine_t e);
 int mpg_engine_step_dots_status(mpg_engine_t e, int k);
+/* CGS update launches of a restart cycle that take the streaming form
+ * (mpg_arnoldi_cgs_stream_at over the cycle's cgs_partials ops; MPG_CGS_PREFETCH) */
+int mpg_engine_cgs_stream_steps(mpg_engine_t e);
 /* block Jacobi: 1 when the apply runs inside the SpMV / residual launches, 0 when it is a
  * launch of its own between them and the dots; -1 for every other preconditioner */
 int mpg_engine_prec_fused(mpg_engine_t e);
