@@ -206,6 +206,7 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_givens_folded.argtypes = [C.c_void_p]
     lib.mpg_engine_step_dots_steps.argtypes = [C.c_void_p]
     lib.mpg_engine_step_dots_status.argtypes = [C.c_void_p, C.c_int]
+    lib.mpg_engine_givens_rider.argtypes = [C.c_void_p]
     lib.mpg_engine_cgs_stream_steps.argtypes = [C.c_void_p]
     lib.mpg_engine_cycle_policy.argtypes = [C.c_void_p, C.POINTER(CyclePolicy)]
     lib.mpg_cycle_plan_describe.argtypes = [C.POINTER(CyclePolicy), C.c_char_p, C.c_int]
@@ -927,7 +928,9 @@ class Engine:
         "col_bytes", "stored"} (mpg_engine_spmv_layout). An engine whose cycle
         runs the SpMV inside the panel dots' launch (MPG_STEP_DOTS) also
         reports "dots_fused": the number of such steps per cycle (the key is
-        absent when there are none), and "cgs_stream": the CGS update launches
+        absent when there are none), "givens_rider": True when those launches
+        carry the folded Givens step on a workgroup of its own
+        (mpg_engine_givens_rider; absent otherwise), and "cgs_stream": the CGS update launches
         per cycle that take the streaming form (MPG_CGS_PREFETCH; absent when
         none). With prec="bjacobi" it reports
         "prec_fused": 1 when the block apply runs inside the SpMV launches, 0
@@ -941,7 +944,9 @@ class Engine:
         pf = int(self._lib.mpg_engine_prec_fused(self._h))
         ps = int(self._lib.mpg_engine_prec_sweeps(self._h))
         stream = int(self._lib.mpg_engine_cgs_stream_steps(self._h))
-        return {**({"dots_fused": fused} if fused > 0 else {}), **({"cgs_stream": stream} if stream > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
+        rider = int(self._lib.mpg_engine_givens_rider(self._h)) == 1
+        return {**({"dots_fused": fused} if fused > 0 else {}), **({"givens_rider": True} if rider else {}),
+                **({"cgs_stream": stream} if stream > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
                 "stored": st.value, "window": bool(win.value),
                 "slices_per_wave": int(self._lib.mpg_engine_slices_per_wave(self._h)),
                 "givens_folded": bool(self._lib.mpg_engine_givens_folded(self._h) == 1),

@@ -1250,7 +1250,7 @@ struct DotsGlobal {
 
 template <class T, int BS, int NC, class A = double, class SRC>
 __device__ __forceinline__ void dots_panel_from(int n, const T* __restrict__ V, int64_t ld, const SRC& src,
-                                           double* __restrict__ partial) {
+                                           double* __restrict__ partial, unsigned G = gridDim.x) {
     static_assert(NC >= 1 && NC <= kNC, "one panel");
     constexpr int NP = Pow2Ceil<NC>::v;
     constexpr int B = kColBatch<T>;
@@ -1293,7 +1293,7 @@ __device__ __forceinline__ void dots_panel_from(int n, const T* __restrict__ V, 
             for (int c = 0; c < NC; ++c) acc[c] += (A)V[(int64_t)c * ld + i] * wi;
         }
     }
-    store_partials<NP, BS>(acc, NC, partial);
+    store_partials<NP, BS>(acc, NC, partial, G);
 }
 
 template <class T, int BS, int NC, class A = double>
@@ -1370,6 +1370,40 @@ __device__ __forceinline__ double wave_first(double v) {
                             __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
+// The fold's ||w||^2 in every lane of a wave, in two parts so that the loads
+// of the first can sit ahead of other work: lane l holds the partials of lane
+// l of the waves 0..NG-1 of a kBlock workgroup (fold_parts_load), and the sum
+// runs with the butterflies and in the order of k_step_sell2's waves 0..3
+// (fold_parts_sum: the same value in every wave and lane).
+template <class T, class A, int NG>
+__device__ __forceinline__ void fold_parts_load(const GivensFold<T>& fold, int lane, A (&part)[NG]) {
+#pragma unroll
+    for (int q = 0; q < NG; ++q) {
+        const int t = q * kWave + lane;
+        part[q] = (A)fold.norm2[t < fold.nparts ? t : 0];
+        if (t >= fold.nparts) part[q] = A(0);
+    }
+}
+template <class T, class A, int NG>
+__device__ __forceinline__ double fold_parts_sum(const GivensFold<T>& fold, const A (&part)[NG]) {
+    if (fold.nparts > 0) {
+        A r = A(0);
+#pragma unroll
+        for (int q = 0; q < NG; ++q) r += wave_first(wave_sum(part[q] + A(0)));
+        return (double)r;
+    }
+    return fold.norm2[0];
+}
+
+// FOLD launches one workgroup more than the dots' grid, the rider: the last
+// block index runs Givens step k - 1 (givens_block) and nothing else, beside
+// the SpMV phase of the others -- on a CU the grid leaves free while it has
+// fewer workgroups than the chip has CUs, behind the first workgroup to
+// retire otherwise. (At the end of workgroup 0, where the split kernels carry
+// the step, it was this launch's tail: one workgroup per CU, all of them
+// ending together, and every CU but one waiting for the rotation chain of one
+// lane.) The rider stores no partials: the others store G = gridDim.x - 1 per
+// column, and nothing they read is written by it.
 template <class T, class P, int W, bool FOLD, int BE, int NC, bool PF, class A>
 __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices, const int16_t* __restrict__ col,
                                                              const T* __restrict__ val, const T* __restrict__ wprev,
@@ -1396,6 +1430,17 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
     __shared__ __attribute__((aligned(16))) T win[NW][WL];
     __shared__ __attribute__((aligned(16))) T wst[RB];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = wave_id();
+    constexpr int NG = kBlock / kWave;
+    if constexpr (FOLD) {
+        if (blockIdx.x == gridDim.x - 1) {  // the rider
+            __shared__ T col_s[kFoldMaxM + 2], c_s[kFoldMaxM + 2], s_s[kFoldMaxM + 2];
+            A part[NG];
+            fold_parts_load(fold, lane, part);
+            givens_block(fold.g, fold_parts_sum(fold, part), col_s, c_s, s_s);
+            return;
+        }
+    }
+    const unsigned G = FOLD ? gridDim.x - 1 : gridDim.x;  // workgroups with rows
     const int base = (int)blockIdx.x * RB;
     const int row0 = base + wid * RW;  // the wave's first row
     const int s0 = (int)blockIdx.x * (RB / kWave) + wid * SPW;
@@ -1408,18 +1453,9 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
         row[p].init_uniform(live_p[p] ? s0 + p : 0, ustride, spat, coff);
     }
     __builtin_amdgcn_sched_barrier(0);
-    // 1. the fold's ||w||^2 partials: lane l of every wave holds those of
-    // lane l of the waves 0..NG-1 of a kBlock workgroup
-    constexpr int NG = kBlock / kWave;
+    // 1. the fold's ||w||^2 partials
     A part[NG];
-    if constexpr (FOLD) {
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const int t = q * kWave + lane;
-            part[q] = (A)fold.norm2[t < fold.nparts ? t : 0];
-            if (t >= fold.nparts) part[q] = A(0);
-        }
-    }
+    if constexpr (FOLD) fold_parts_load(fold, lane, part);
     __builtin_amdgcn_sched_barrier(0);
     // 2. the wave's window of w_prev, raw: the lane's own row group and one
     // entry each of the 64 rows below and above the wave's (clamped addresses;
@@ -1462,21 +1498,8 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
     }
     __builtin_amdgcn_sched_barrier(0);
     T inv;
-    double nrm2sq = 0.0;
-    if constexpr (FOLD) {
-        // (the same value in every wave and lane: workgroup 0 hands any of them to givens_block)
-        if (fold.nparts > 0) {
-            A r = A(0);
-#pragma unroll
-            for (int q = 0; q < NG; ++q) r += wave_first(wave_sum(part[q] + A(0)));
-            nrm2sq = (double)r;
-        } else {
-            nrm2sq = fold.norm2[0];
-        }
-        inv = inv_of_norm2<T>(nrm2sq);
-    } else {
-        inv = *inv_p;
-    }
+    if constexpr (FOLD) inv = inv_of_norm2<T>(fold_parts_sum(fold, part));  // (the rider's value, formed per wave)
+    else inv = *inv_p;
     // the window of v_k = T(w_prev * inv), zero outside [0, n)
     {
         T vq[4];
@@ -1504,17 +1527,16 @@ __global__ __launch_bounds__(kCombineBlock) void k_step_dots(int n, int nslices,
         if (live_p[p] && i < n) {
             const T t = (T)sum[p];  // spmv(1, A, v, 0, w): y = 1*t
             wi = precond<T, P>(t, diag, i);
+            // (plain dword stores: as two 16-B write-through stores per lane behind the
+            // hand-off below, which leave the launch's end nothing to flush, the kernel
+            // took 0.3 us longer and the bench lost 0.6 %, profiles/r12_step_tail/)
             w[i] = wi;
             V[(int64_t)k * ld + i] = wwin[i - row0 + kWinLo];
         }
         wst[i - base] = wi;  // rows past n: an exact 0, and no row group of theirs is read
     }
     wave_lds_handoff();  // the wave's rows of w and v_k go to its own lanes (the identity above)
-    dots_panel_from<T, BS, NC, A>(n, V, ld, src, dpart);
-    if constexpr (FOLD) {
-        __shared__ T col_s[kFoldMaxM + 2], c_s[kFoldMaxM + 2], s_s[kFoldMaxM + 2];
-        if (blockIdx.x == 0) givens_block(fold.g, nrm2sq, col_s, c_s, s_s);
-    }
+    dots_panel_from<T, BS, NC, A>(n, V, ld, src, dpart, G);
 }
 
 // V^T w for nc > kNC columns in ONE launch (GMRES(100): the round-3 form ran

@@ -261,7 +261,8 @@ int step_dots_run(mpg_arnoldi_t a, int k, int fold) {
         int st = with_nc<kNC>(k + 1, [&](auto nc) {
             constexpr int NC = decltype(nc)::value;
             auto go = [&](auto kern) {
-                launch_timed(a->ctx, kern, dim3(a->Gd), dim3(kCombineBlock), a->d.n, S.nslices,
+                // (with the fold one workgroup more, last in the grid: the rider that runs the Givens step)
+                launch_timed(a->ctx, kern, dim3(a->Gd + (fold ? 1 : 0)), dim3(kCombineBlock), a->d.n, S.nslices,
                              static_cast<const int16_t*>(S.col), static_cast<const T*>(S.val),
                              static_cast<const T*>(a->w[k & 1]), static_cast<const T*>(a->inv()),
                              static_cast<T*>(a->V), a->ld, k, diag, static_cast<T*>(a->w[(k + 1) & 1]), gf, S.spat,

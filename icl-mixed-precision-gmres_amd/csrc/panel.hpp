@@ -30,7 +30,8 @@ __device__ __forceinline__ void butterfly_round(A (&acc)[N], int lane) {
 // Block-reduce NCOL accumulators (fp64, or fp32 under the fp32
 // accumulation class: every add of the trees below rounds to fp32) and store
 // them as partial[c*G + blk] (fp64 storage; write-through when WT: the
-// last-arriver combine reads them).
+// last-arriver combine reads them). G: the workgroups that store partials,
+// the whole grid unless the launch carries one that stores none (k_step_dots).
 //
 // Wave stage = transpose (butterfly) reduction: in round r every lane trades
 // half of its remaining columns with the lane 32>>r away and keeps the sum
@@ -39,7 +40,8 @@ __device__ __forceinline__ void butterfly_round(A (&acc)[N], int lane) {
 // finish the remaining lanes. 32 columns cost 32 shuffles instead of the
 // 192 of one 6-level reduction per column. Fixed order: deterministic.
 template <int NCOL, int BS = kBlock, bool WT = false, class A>
-__device__ __forceinline__ void store_partials(A (&acc)[NCOL], int ncols, double* __restrict__ partial) {
+__device__ __forceinline__ void store_partials(A (&acc)[NCOL], int ncols, double* __restrict__ partial,
+                                               unsigned G = gridDim.x) {
     static_assert((NCOL & (NCOL - 1)) == 0 && NCOL <= 32, "NCOL: power of two <= 32");
     __shared__ A red[BS / kWave][NCOL];
     const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
@@ -55,8 +57,8 @@ __device__ __forceinline__ void store_partials(A (&acc)[NCOL], int ncols, double
         A s = A(0);
 #pragma unroll
         for (int w = 0; w < BS / kWave; ++w) s += red[w][c];
-        if (WT) store_wt(partial + (size_t)c * gridDim.x + blockIdx.x, (double)s);
-        else partial[(size_t)c * gridDim.x + blockIdx.x] = (double)s;
+        if (WT) store_wt(partial + (size_t)c * G + blockIdx.x, (double)s);
+        else partial[(size_t)c * G + blockIdx.x] = (double)s;
     }
 }
 

@@ -1007,6 +1007,9 @@ int FusedEngine::prec_sweeps() const { return p_->nm_asked ? p_->nm_asked : -1; 
 int FusedEngine::step_dots_steps() const {
     return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::StepDots; });
 }
+bool FusedEngine::givens_rider() const {  // (StepDots: a = k, b = the fold)
+    return std::any_of(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::StepDots && o.b != 0; });
+}
 int FusedEngine::cgs_stream_steps() const {
     return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [&](const Op& o) {
         return o.kind == OpKind::CgsPartials && mpg_arnoldi_cgs_stream_at(p_->arn, o.a) == 1;
@@ -1150,6 +1153,11 @@ int mpg_engine_givens_folded(mpg_engine_t e) {
 int mpg_engine_step_dots_steps(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return e->eng->step_dots_steps();
+}
+
+int mpg_engine_givens_rider(mpg_engine_t e) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return e->eng->givens_rider() ? 1 : 0;
 }
 
 int mpg_engine_cgs_stream_steps(mpg_engine_t e) {

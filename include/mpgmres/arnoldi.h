@@ -196,7 +196,8 @@ int mpg_arnoldi_spmv_dots_supported(mpg_arnoldi_t a, int k);
  * of 1024-lane workgroups, each forming its own 4096 rows of w and v_k, then
  * the panel dots on them from LDS -- replaces spmv + dots ahead of
  * mpg_arnoldi_cgs_partials with the same bits and the same partials (one GPU,
- * plain CGS, k + 1 <= 32). MPG_ERR_UNSUPPORTED unless: fp32 accumulation
+ * plain CGS, k + 1 <= 32). With a fold the grid has one workgroup more, which
+ * runs the Givens step and nothing else. MPG_ERR_UNSUPPORTED unless: fp32 accumulation
  * (mpg_arnoldi_set_accum), fp32 basis and values, the uniform SELL copy of
  * int16 column pairs with 10 entries per row and the v_k window, no halo
  * rows, n % 4 == 0 and n <= 1,048,576 (one pass). _supported returns the

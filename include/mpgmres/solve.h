@@ -196,6 +196,9 @@ int mpg_engine_givens_folded(mpg_engine_t e);
  * support check gives at step k (MPG_OK / MPG_ERR_UNSUPPORTED) */
 int mpg_engine_step_dots_steps(mpg_engine_t e);
 int mpg_engine_step_dots_status(mpg_engine_t e, int k);
+/* 1: those launches carry the Givens step of step k-1 on a workgroup of its own, the
+ * last of the grid (k_step_dots' rider); 0: no such launch, or the step is not folded */
+int mpg_engine_givens_rider(mpg_engine_t e);
 /* CGS update launches of a restart cycle that take the streaming form
  * (mpg_arnoldi_cgs_stream_at over the cycle's cgs_partials ops; MPG_CGS_PREFETCH) */
 int mpg_engine_cgs_stream_steps(mpg_engine_t e);
