@@ -208,6 +208,7 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_step_dots_status.argtypes = [C.c_void_p, C.c_int]
     lib.mpg_engine_givens_rider.argtypes = [C.c_void_p]
     lib.mpg_engine_cgs_stream_steps.argtypes = [C.c_void_p]
+    lib.mpg_engine_tail_fold.argtypes = [C.c_void_p]
     lib.mpg_engine_cycle_policy.argtypes = [C.c_void_p, C.POINTER(CyclePolicy)]
     lib.mpg_cycle_plan_describe.argtypes = [C.POINTER(CyclePolicy), C.c_char_p, C.c_int]
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
@@ -302,6 +303,20 @@ _HIP_DECLS.update({
     "mpg_arnoldi_spmv": ([_P, C.c_int], C.c_int),
     "mpg_arnoldi_wprev_dev": ([_P, C.c_int], _P),
     "mpg_arnoldi_inv_dev": ([_P], _P),
+    "mpg_arnoldi_rotations_dev": ([_P, C.c_int], _P),
+    "mpg_arnoldi_hessenberg_dev": ([_P], _P),
+    "mpg_arnoldi_report_dev": ([_P], _P),
+    "mpg_arnoldi_report_len": ([_P], C.c_int),
+    "mpg_arnoldi_prologue": ([_P], C.c_int),
+    "mpg_arnoldi_prologue_finish_partials": ([_P], C.c_int),
+    "mpg_arnoldi_dots": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_cgs_partials": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_givens_partials": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_givens_partials_spmv": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_update": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_update_tail": ([_P, C.c_int, C.c_int], C.c_int),
+    "mpg_arnoldi_update_tail_supported": ([_P], C.c_int),
+    "mpg_arnoldi_set_x_snapshot": ([_P, _P], C.c_int),
     "mpg_arnoldi_spmv_layout": ([_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64),
                                  C.POINTER(_I32)], C.c_int),
     "mpg_nrm2_pair_host": ([_P, _I64, C.c_int, _P, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)],
@@ -932,7 +947,9 @@ class Engine:
         carry the folded Givens step on a workgroup of its own
         (mpg_engine_givens_rider; absent otherwise), and "cgs_stream": the CGS update launches
         per cycle that take the streaming form (MPG_CGS_PREFETCH; absent when
-        none). With prec="bjacobi" it reports
+        none), and "tail_fold": True when the cycle ends with the one
+        givens+update launch (MPG_TAIL_FOLD, mpg_engine_tail_fold; absent
+        otherwise). With prec="bjacobi" it reports
         "prec_fused": 1 when the block apply runs inside the SpMV launches, 0
         when it is a launch of its own (mpg_engine_prec_fused). With
         prec="neumann" it reports "prec_sweeps": the Jacobi sweeps per
@@ -945,7 +962,9 @@ class Engine:
         ps = int(self._lib.mpg_engine_prec_sweeps(self._h))
         stream = int(self._lib.mpg_engine_cgs_stream_steps(self._h))
         rider = int(self._lib.mpg_engine_givens_rider(self._h)) == 1
+        tail = int(self._lib.mpg_engine_tail_fold(self._h)) == 1
         return {**({"dots_fused": fused} if fused > 0 else {}), **({"givens_rider": True} if rider else {}),
+                **({"tail_fold": True} if tail else {}),
                 **({"cgs_stream": stream} if stream > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
                 "stored": st.value, "window": bool(win.value),
                 "slices_per_wave": int(self._lib.mpg_engine_slices_per_wave(self._h)),

@@ -163,6 +163,7 @@ class CyclePolicy(C.Structure):
         "sep_prec_step", "sep_prec_prologue", "partials_max_cols", "fold_max_m")] + [
         ("step_dots_ok", C.c_uint8 * CYCLE_POLICY_STEPS),
         ("spmv_dots_ok", C.c_uint8 * CYCLE_POLICY_STEPS),
+        ("tail_fold", C.c_int32),
     ]
 
 

@@ -163,7 +163,7 @@ int mpg_arnoldi_create(mpg_ctx_t ctx, const mpg_arnoldi_desc* desc, mpg_arnoldi_
         return hipMemsetAsync(*p, 0, bytes ? bytes : 16, ctx->stream) == hipSuccess;
     };
     bool ok = alloc(&a->V, (size_t)a->ld * (m + 1) * a->tsize) && alloc(&a->H, (size_t)(m + 1) * m * a->tsize) &&
-              alloc(&a->small, (size_t)6 * (m + 1) * a->tsize) &&
+              alloc(&a->small, (size_t)7 * (m + 1) * a->tsize) &&  // (slot 6: tail_stage)
               alloc(&a->wbase[0], (size_t)(a->front + desc->n_ext + 64) * a->tsize) &&
               alloc(&a->wbase[1], (size_t)(a->front + desc->n_ext + 64) * a->tsize) &&
               alloc((void**)&a->partial, std::max<size_t>(std::max<size_t>((size_t)(kNC + 4) * a->Grb,
@@ -351,15 +351,22 @@ int mpg_arnoldi_prologue_finish_partials(mpg_arnoldi_t a) {
     int st = dispatch(a->combo, [&](auto t, auto x, auto, auto) {
         using T = decltype(t);
         using X = decltype(x);
+        // the rotated column a givens+update launch left staged (mpg_arnoldi_update_tail)
+        const int m = a->d.m;
+        const T* stage = a->tail_staged ? static_cast<const T*>(a->tail_stage()) : nullptr;
+        T* hcol = static_cast<T*>(a->H) + (int64_t)(m - 1) * (m + 1);
         if (a->last_G <= 2 * kBlock)
             k_prologue_finish_parts<T, X, kBlock><<<1, kBlock, 0, a->ctx->stream>>>(
-                a->last_G, a->last_part, a->sums, a->d.m, static_cast<T*>(a->s()), static_cast<T*>(a->inv()), a->report);
+                a->last_G, a->last_part, a->sums, m, static_cast<T*>(a->s()), static_cast<T*>(a->inv()), a->report,
+                stage, hcol);
         else
             k_prologue_finish_parts<T, X, 1024><<<1, 1024, 0, a->ctx->stream>>>(
-                a->last_G, a->last_part, a->sums, a->d.m, static_cast<T*>(a->s()), static_cast<T*>(a->inv()), a->report);
+                a->last_G, a->last_part, a->sums, m, static_cast<T*>(a->s()), static_cast<T*>(a->inv()), a->report,
+                stage, hcol);
         return MPG_OK;
     });
     if (st) return st;
+    a->tail_staged = false;
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
 }
@@ -429,6 +436,20 @@ int mpg_arnoldi_givens_partials(mpg_arnoldi_t a, int k) { return givens_impl(a, 
 
 int mpg_arnoldi_update(mpg_arnoldi_t a, int k) {
     return a && a->acc32 ? mpg_acc32::update(a, k) : update_run<double>(a, k);
+}
+int mpg_arnoldi_update_tail(mpg_arnoldi_t a, int m, int flags) {
+    return a && a->acc32 ? mpg_acc32::update_tail(a, m, flags) : update_tail_run<double>(a, m, flags);
+}
+int mpg_arnoldi_update_tail_supported(mpg_arnoldi_t a) {
+    return !a ? MPG_ERR_ARG : update_tail_ok(a) ? MPG_OK : MPG_ERR_UNSUPPORTED;
+}
+const void* mpg_arnoldi_rotations_dev(mpg_arnoldi_t a, int which) {
+    return !a ? nullptr : which == 0 ? a->cs() : which == 1 ? a->sn() : which == 2 ? a->s() : nullptr;
+}
+int mpg_arnoldi_set_x_snapshot(mpg_arnoldi_t a, void* x_snap) {
+    if (!a) return MPG_ERR_ARG;
+    a->x_snap = x_snap;
+    return MPG_OK;
 }
 
 int mpg_arnoldi_set_accum(mpg_arnoldi_t a, int accum) {

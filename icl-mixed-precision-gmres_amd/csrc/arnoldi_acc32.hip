@@ -18,4 +18,5 @@ int cgs(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool n
 int mgs(mpg_arnoldi* a, int k, int j, bool from_partials) { return mgs_run<float>(a, k, j, from_partials); }
 int givens(mpg_arnoldi* a, int k, bool from_partials) { return givens_run<float>(a, k, from_partials); }
 int update(mpg_arnoldi* a, int k) { return update_run<float>(a, k); }
+int update_tail(mpg_arnoldi* a, int m, int flags) { return update_tail_run<float>(a, m, flags); }
 }  // namespace mpg_acc32

@@ -605,6 +605,46 @@ int update_run(mpg_arnoldi_t a, int k) {
 }
 
 
+// givens_partials(m - 1) + update(m) (+ the x snapshot, flags bit 0) in one
+// launch (k_update_tail_nc): the whole restart length in one panel, and the
+// ||w||^2 partials of a 1024-thread producer (at most kBlock of them, which
+// fold_parts_sum adds in k_givens' order). Asked without launching:
+// update_tail_ok.
+inline bool update_tail_ok(const mpg_arnoldi* a) {
+    return a && a->d.m >= 1 && a->d.m <= kNC && a->Gd <= kBlock;
+}
+
+template <class A>
+int update_tail_run(mpg_arnoldi_t a, int m, int flags) {
+    if (!update_tail_ok(a)) return a ? MPG_ERR_UNSUPPORTED : MPG_ERR_ARG;
+    if (m != a->d.m || (flags & ~1) || a->last_G < 1 || a->last_G > kBlock) return MPG_ERR_ARG;
+    if ((flags & 1) && !a->x_snap) return MPG_ERR_ARG;
+    int st = dispatch_acc<A>(a->combo, [&](auto t, auto x, auto, auto) {
+        using T = decltype(t);
+        using X = decltype(x);
+        const UpdateTail<T> tl{GivensFold<T>{a->last_part, a->last_G, givens_args<T>(a, m - 1)},
+                               static_cast<T*>(a->tail_stage())};
+        return with_nc<kNC>(m, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value;
+            constexpr bool stream = std::is_same_v<T, float> && std::is_same_v<A, float>;
+            const T* Vp = static_cast<const T*>(a->V);
+            X* xp = static_cast<X*>(a->d.x);
+            if (flags & 1)
+                k_update_tail_nc<T, X, NC, A, stream, true><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
+                    a->d.n, Vp, a->ld, xp, static_cast<X*>(a->x_snap), tl);
+            else
+                k_update_tail_nc<T, X, NC, A, stream, false><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
+                    a->d.n, Vp, a->ld, xp, nullptr, tl);
+            return (int)MPG_OK;
+        });
+    });
+    if (st) return st;
+    a->tail_staged = true;  // the next finish launch copies the staged column into H
+    MPG_LAUNCH_CHECK(a->ctx);
+    return MPG_OK;
+}
+
+
 }  // namespace
 
 // The A = float launches, compiled in arnoldi_acc32.hip (fp32 Arnoldi only:
@@ -621,4 +661,5 @@ int cgs(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool n
 int mgs(mpg_arnoldi* a, int k, int j, bool from_partials);
 int givens(mpg_arnoldi* a, int k, bool from_partials);
 int update(mpg_arnoldi* a, int k);
+int update_tail(mpg_arnoldi* a, int m, int flags);
 }  // namespace mpg_acc32

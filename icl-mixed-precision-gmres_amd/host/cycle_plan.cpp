@@ -1,6 +1,7 @@
 // The restart cycle's op list (cycle_plan.hpp) and its text form.
 #include "cycle_plan.hpp"
 
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 
@@ -19,8 +20,9 @@ constexpr struct {
     {"allreduce_partials", 1}, {"reduce", 1}, {"allreduce_sums", 1}, {"cgs_partials", 1}, {"cgs", 2},
     {"cgs_givens", 2}, {"cgsr_wide_pass", 2}, {"mgs_partials", 2}, {"givens", 1}, {"givens_partials", 1},
     {"update", 1}, {"prologue", 0}, {"prologue_wnorm", 0}, {"prologue_finish", 0}, {"prologue_finish_partials", 0},
+    {"givens+update", 2},
 };
-static_assert(sizeof kOpNames / sizeof kOpNames[0] == (size_t)OpKind::PrologueFinishPartials + 1, "one name per kind");
+static_assert(sizeof kOpNames / sizeof kOpNames[0] == (size_t)OpKind::GivensUpdate + 1, "one name per kind");
 
 struct Builder {
     const CyclePolicy& p;
@@ -156,12 +158,22 @@ void plan_prologue(const CyclePolicy& p, std::vector<Op>& out) {
 
 int plan_cycle(const CyclePolicy& p, std::vector<Op>& out) {
     if (p.m < 1) return MPG_ERR_ARG;
-    if (p.pipeline) out.push_back(Op{OpKind::XSnapshot, -1, false, 0, 0, 0});
+    const size_t head = out.size();
     for (int k = 0; k < p.m; ++k)
         if (int st = plan_step(p, k, p.fold != 0, out)) return st;
     Builder B{p, out};
     if (p.fold) B.givens(p.m - 1);
-    B.op(OpKind::Update, p.m);
+    // the cycle's tail in one launch: the last Givens step, the update and
+    // the snapshot of the x it overwrites (the next cycle's undo)
+    const bool tail = p.tail_fold && !B.ranks() && p.m <= 32 && out.size() > head &&
+                      out.back().kind == OpKind::GivensPartials && out.back().a == p.m - 1;
+    if (tail) {
+        out.pop_back();
+        B.op(OpKind::GivensUpdate, p.m, p.pipeline ? 1 : 0);
+    } else {
+        if (p.pipeline) out.insert(out.begin() + (std::ptrdiff_t)head, Op{OpKind::XSnapshot, -1, false, 0, 0, 0});
+        B.op(OpKind::Update, p.m);
+    }
     plan_prologue(p, out);
     return MPG_OK;
 }

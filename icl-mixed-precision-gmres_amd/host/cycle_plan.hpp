@@ -18,10 +18,13 @@ using CyclePolicy = mpg_cycle_policy;
 // One kind per distinct call of the cycle: FusedEngine::issue maps each to
 // its mpg_arnoldi_* / Comm call, kOpNames (cycle_plan.cpp, this order) to
 // its spelling. Halo: of w_prev(a), a < 0: of x. ApplyPrec: M^-1 on w_prev(a).
+// GivensUpdate(m, flags): Givens step m-1 and update(m) in one launch
+// (policy.tail_fold); flags bit 0: the launch also keeps the x it read (the
+// cycle then has no XSnapshot).
 enum class OpKind : uint8_t {
     XSnapshot, Halo, AllreducePartialsHalo, Spmv, GivensSpmv, SpmvDots, StepDots, ApplyPrec, Dots, DotsSums,
     AllreducePartials, Reduce, AllreduceSums, CgsPartials, Cgs, CgsGivens, CgsrWidePass, MgsPartials, Givens,
-    GivensPartials, Update, Prologue, PrologueWnorm, PrologueFinish, PrologueFinishPartials,
+    GivensPartials, Update, Prologue, PrologueWnorm, PrologueFinish, PrologueFinishPartials, GivensUpdate,
 };
 
 struct Op {
@@ -35,7 +38,9 @@ struct Op {
 // Append step k's ops (fold: Givens(k-1) rides this step's SpMV launch and
 // step k's own Givens is left to the next step / the caller), the residual
 // prologue's, a whole cycle's (snapshot, steps 0..m-1, the trailing Givens
-// step if folded, update(m), prologue). MPG_OK, or MPG_ERR_UNSUPPORTED where
+// step if folded, update(m), prologue; with policy.tail_fold on one GPU and
+// m <= 32, a givens_partials(m-1) directly ahead of update(m) and the
+// snapshot go into the one givens+update launch). MPG_OK, or MPG_ERR_UNSUPPORTED where
 // a required launch (step_dots / fuse_dots = 2) cannot be taken.
 int plan_step(const CyclePolicy& p, int k, bool fold, std::vector<Op>& out);
 void plan_prologue(const CyclePolicy& p, std::vector<Op>& out);

@@ -296,6 +296,14 @@ void FusedEngine::Impl::resolve_policy() {
         fold_on = any_no == 0.0;
     }
     P.fold = !P.combine && fold_on && m <= P.fold_max_m;
+    // MPG_TAIL_FOLD: the last Givens step, update(m) and the x snapshot in
+    // the one givens+update launch, where the workspace builds it (one GPU,
+    // m <= 32). 0 never, 1 wherever built; unset: in the fp32 accumulation
+    // class, where it was measured (BAND-10M, profiles/r13_cycle_tail/) and
+    // the columns stream through LDS; the fp64 class keeps the launches it had.
+    const char tenv = env("MPG_TAIL_FOLD");
+    const bool tail_on = tenv ? tenv != '0' : mpg_arnoldi_accum(arn) == MPG_ACCUM_F32;
+    P.tail_fold = !comm && tail_on && mpg_arnoldi_update_tail_supported(arn) == MPG_OK;
     if (int st = plan_cycle(P, cycle))
         throw StatusError(st, "MPG_STEP_DOTS=2 / MPG_FUSE_DOTS=2: a step of the cycle cannot take the required SpMV + "
                               "dots launch (one GPU, plain CGS with in-launch sums, no preconditioner launch -- ILU, "
@@ -558,6 +566,13 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
 
     I.resolve_policy();
     if (I.pol.pipeline) I.x_snap = DevMem(ctx, I.x.bytes);
+    if (I.pol.pipeline && tail_fold()) {
+        // the givens+update launch keeps rows [0, n) of the x it reads; the
+        // restore copies the whole array, so its padding is filled here, once
+        hipck(hipMemcpyAsync(I.x_snap.p, I.x.p, I.x.bytes, hipMemcpyDeviceToDevice, I.stream()), "x snapshot");
+        check(mpg_arnoldi_set_x_snapshot(I.arn, static_cast<char*>(I.x_snap.p) + (size_t)I.front * dsize(I.ty.X)),
+              "x snapshot", ctx);
+    }
     check(mpg_ctx_sync(ctx), "sync", ctx);
     setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
     prologue();
@@ -606,6 +621,7 @@ void FusedEngine::issue(const Op& o) {
         case OpKind::Givens: return check(mpg_arnoldi_givens(A, o.a), "givens", I.ctx);
         case OpKind::GivensPartials: return check(mpg_arnoldi_givens_partials(A, o.a), "givens", I.ctx);
         case OpKind::Update: return check(mpg_arnoldi_update(A, o.a), "update", I.ctx);
+        case OpKind::GivensUpdate: return check(mpg_arnoldi_update_tail(A, o.a, o.b), "givens+update", I.ctx);
         case OpKind::Prologue: return check(mpg_arnoldi_prologue(A), "prologue", I.ctx);
         case OpKind::PrologueWnorm: return check(mpg_arnoldi_prologue_wnorm(A), "prologue wnorm", I.ctx);
         case OpKind::PrologueFinish: return check(mpg_arnoldi_prologue_finish(A), "prologue_finish", I.ctx);
@@ -1010,6 +1026,9 @@ int FusedEngine::step_dots_steps() const {
 bool FusedEngine::givens_rider() const {  // (StepDots: a = k, b = the fold)
     return std::any_of(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::StepDots && o.b != 0; });
 }
+bool FusedEngine::tail_fold() const {
+    return std::any_of(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::GivensUpdate; });
+}
 int FusedEngine::cgs_stream_steps() const {
     return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [&](const Op& o) {
         return o.kind == OpKind::CgsPartials && mpg_arnoldi_cgs_stream_at(p_->arn, o.a) == 1;
@@ -1160,6 +1179,9 @@ int mpg_engine_givens_rider(mpg_engine_t e) {
     return e->eng->givens_rider() ? 1 : 0;
 }
 
+int mpg_engine_tail_fold(mpg_engine_t e) {
+    return e && e->eng ? (e->eng->tail_fold() ? 1 : 0) : -1;
+}
 int mpg_engine_cgs_stream_steps(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return e->eng->cgs_stream_steps();

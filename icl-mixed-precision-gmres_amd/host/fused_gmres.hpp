@@ -149,6 +149,7 @@ public:
     int cgs_stream_steps() const;      // CGS update launches of a cycle that take the streaming form
     int step_dots_steps() const;       // steps of a cycle that run the SpMV inside the dots' launch
     bool givens_rider() const;         // ... and one of them folds the Givens step (k_step_dots' rider workgroup)
+    bool tail_fold() const;            // the cycle ends with the givens+update launch (mpg_arnoldi_update_tail)
     void sync();
     const CyclePolicy& policy() const;  // mpg_engine_cycle_policy
 

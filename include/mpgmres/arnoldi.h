@@ -217,6 +217,20 @@ int mpg_arnoldi_fold_max_m(void);
  * launch costs less); the engine folds then unless MPG_FOLD_GIVENS says */
 int mpg_arnoldi_fold_pays(mpg_arnoldi_t a);
 int mpg_arnoldi_update(mpg_arnoldi_t a, int k);
+/* mpg_arnoldi_givens_partials(a, m - 1) and mpg_arnoldi_update(a, m) in one
+ * launch, for the whole restart length m <= 32 on one GPU, with the same
+ * bits: every workgroup requests its rows of x and of the first basis columns,
+ * runs the Givens step and the upper solve while they arrive, then adds the
+ * columns. flags bit 0: the x read is also stored to the snapshot buffer
+ * (mpg_arnoldi_set_x_snapshot: row 0 of an array laid out as x). The launch
+ * stores cs, sn, 1/h and the report entry of step m - 1 in place; the rotated
+ * column H(0..m, m-1) waits in the workspace until the next
+ * mpg_arnoldi_prologue_finish_partials copies it into H (the launch's own
+ * workgroups read that column), and s is left for that launch to reset.
+ * _supported returns the status the launch would, without launching. */
+int mpg_arnoldi_update_tail(mpg_arnoldi_t a, int m, int flags);
+int mpg_arnoldi_update_tail_supported(mpg_arnoldi_t a);
+int mpg_arnoldi_set_x_snapshot(mpg_arnoldi_t a, void* x_snap);
 /* sums[c] = sum over workgroups of partial column c, c < ncols */
 int mpg_arnoldi_reduce(mpg_arnoldi_t a, int ncols);
 
@@ -234,6 +248,8 @@ const void* mpg_arnoldi_hessenberg_dev(mpg_arnoldi_t a);  /* (m+1) x m, column-m
 /* 1/h_{k+1,k} (T) written by the Givens step k for the next SpMV's
  * normalisation (Orthogonalization.hpp:56-59 reciprocal) */
 const void* mpg_arnoldi_inv_dev(mpg_arnoldi_t a);
+/* the Givens state, m + 1 values of T each: which = 0 cs, 1 sn, 2 s; NULL otherwise */
+const void* mpg_arnoldi_rotations_dev(mpg_arnoldi_t a, int which);
 /* measurement: the next Arnoldi SpMV launch (any form: plain, Givens folded,
  * dots fused) records its own kernel start/stop on these hipEvent_t
  * (hipExtLaunchKernel events: the kernel alone, not the queue around it) */

@@ -199,6 +199,8 @@ int mpg_engine_step_dots_status(mpg_engine_t e, int k);
 /* 1: those launches carry the Givens step of step k-1 on a workgroup of its own, the
  * last of the grid (k_step_dots' rider); 0: no such launch, or the step is not folded */
 int mpg_engine_givens_rider(mpg_engine_t e);
+/* 1: the cycle ends with the givens+update launch (mpg_arnoldi_update_tail; MPG_TAIL_FOLD), 0: it does not */
+int mpg_engine_tail_fold(mpg_engine_t e);
 /* CGS update launches of a restart cycle that take the streaming form
  * (mpg_arnoldi_cgs_stream_at over the cycle's cgs_partials ops; MPG_CGS_PREFETCH) */
 int mpg_engine_cgs_stream_steps(mpg_engine_t e);
@@ -249,6 +251,8 @@ typedef struct {
     int32_t fold_max_m;        /* mpg_arnoldi_fold_max_m() */
     uint8_t step_dots_ok[MPG_CYCLE_POLICY_STEPS]; /* mpg_arnoldi_step_dots_supported(k) == MPG_OK */
     uint8_t spmv_dots_ok[MPG_CYCLE_POLICY_STEPS]; /* mpg_arnoldi_spmv_dots_supported(k) == MPG_OK */
+    int32_t tail_fold;         /* one GPU, m <= 32: the last Givens step, update(m) and the x snapshot in one launch
+                                  (MPG_TAIL_FOLD, mpg_arnoldi_update_tail_supported); 0: their own launches */
 } mpg_cycle_policy;
 /* The launches and collectives of one restart cycle under `p`, in order, as
  * text: one token per op, separated by single spaces, NUL-terminated and cut

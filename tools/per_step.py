@@ -4,7 +4,7 @@ each Arnoldi step k (its occurrence index within a cycle), and a least-squares
 fit t(k) = a + b*k, which separates a launch's fixed cost (a) from the cost of
 each added basis column (b).
 
-A cycle starts at k_prologue / k_prologue_sell (or k_update_x closes one); k counts the
+A cycle starts at k_prologue / k_prologue_sell (k_update_x / k_update_tail closes one); k counts the
 occurrences of each kernel name since the cycle started.
 
 usage: python tools/per_step.py gpurun_out/prof/.../kernel_trace.csv [col_bytes]
@@ -35,7 +35,7 @@ def main():
         if cur is None:
             continue
         cur.append((k, d))
-        if k.startswith("k_update_x"):
+        if k.startswith(("k_update_x", "k_update_tail")):
             cycles.append(cur)
             cur = None
     # keep the cycles of the most common shape (drops eagerly timed cycles
