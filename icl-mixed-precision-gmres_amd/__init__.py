@@ -214,6 +214,8 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_fused.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_sweeps.argtypes = [C.c_void_p]
+    lib.mpg_engine_prec_interval.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.mpg_cheb_coeffs.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.mpg_engine_prologue_format.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.restype = C.c_int64
@@ -297,6 +299,13 @@ _HIP_DECLS.update({
     "mpg_sell_jacobi_sweep_f64": ([_P, _P, _P, _P, _P, _P], C.c_int),
     "mpg_sell_jacobi_sweep_f32": ([_P, _P, _P, _P, _P, _P], C.c_int),
     "mpg_arnoldi_neumann_apply": ([_P, _I32, _P, _P, _P], C.c_int),
+    "mpg_csr_cheb_sweep_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double], C.c_int),
+    "mpg_csr_cheb_sweep_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float], C.c_int),
+    "mpg_sell_cheb_sweep_f64": ([_P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double], C.c_int),
+    "mpg_sell_cheb_sweep_f32": ([_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float], C.c_int),
+    "mpg_csr_jacobi_bound_f64": ([_P, _P, _P, _P, C.POINTER(C.c_double)], C.c_int),
+    "mpg_csr_jacobi_bound_f32": ([_P, _P, _P, _P, C.POINTER(C.c_double)], C.c_int),
+    "mpg_arnoldi_cheb_apply": ([_P, _I32, C.c_double, C.c_double, _P, _P, _P], C.c_int),
     "mpg_arnoldi_create": ([_P, _P, C.POINTER(_P)], C.c_int),
     "mpg_arnoldi_destroy": ([_P], C.c_int),
     "mpg_arnoldi_set_accum": ([_P, C.c_int], C.c_int),
@@ -952,14 +961,18 @@ class Engine:
         otherwise). With prec="bjacobi" it reports
         "prec_fused": 1 when the block apply runs inside the SpMV launches, 0
         when it is a launch of its own (mpg_engine_prec_fused). With
-        prec="neumann" it reports "prec_sweeps": the Jacobi sweeps per
-        application (mpg_engine_prec_sweeps)."""
+        prec="neumann" and prec="chebyshev" it reports "prec_sweeps": the
+        sweeps per application (mpg_engine_prec_sweeps); with prec="chebyshev"
+        also "prec_interval": the interval (a, b) its coefficients were built
+        for (mpg_engine_prec_interval)."""
         f, w, cb, st, win = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         if self._lib.mpg_engine_spmv_layout(self._h, C.byref(f), C.byref(w), C.byref(cb), C.byref(st), C.byref(win)):
             raise RuntimeError("mpg_engine_spmv_layout failed")
         fused = int(self._lib.mpg_engine_step_dots_steps(self._h))
         pf = int(self._lib.mpg_engine_prec_fused(self._h))
         ps = int(self._lib.mpg_engine_prec_sweeps(self._h))
+        ia, ib = C.c_double(), C.c_double()
+        has_iv = self._lib.mpg_engine_prec_interval(self._h, C.byref(ia), C.byref(ib)) == 0
         stream = int(self._lib.mpg_engine_cgs_stream_steps(self._h))
         rider = int(self._lib.mpg_engine_givens_rider(self._h)) == 1
         tail = int(self._lib.mpg_engine_tail_fold(self._h)) == 1
@@ -972,6 +985,7 @@ class Engine:
                 "accum": {0: "f64", 1: "f32"}[int(self._lib.mpg_engine_accum(self._h))],
                 **({"prec_fused": pf} if pf >= 0 else {}),
                 **({"prec_sweeps": ps} if ps >= 0 else {}),
+                **({"prec_interval": (ia.value, ib.value)} if has_iv else {}),
                 "prologue": {1: "csr", 2: "sell", 3: "node"}[int(self._lib.mpg_engine_prologue_format(self._h))]}
 
     def step_dots_status(self, k: int) -> int:

@@ -18,7 +18,21 @@
 // every copy (int32, int16, stepped and implicit columns, sorted rows, the
 // stepped form's CSR-summed slices), in XCD slice order: the row sum's order
 // does not depend on the SpMV's window or pair forms, so the bits are theirs.
+//
+// The Chebyshev polynomial on [a, b] (theta = (a + b) / 2, delta = (b - a) / 2)
+// runs through the same launches with another epilogue (the template
+// parameter E): z_1 = (1 / theta) D r, then
+//
+//   z_out[i] = z_in[i] + alpha (z_in[i] - z_prev[i]) + beta d[i] (r[i] - s_i)
+//
+// in seven separately rounded operations (sweep_update below), alpha and beta from
+// mpg_cheb_coeffs. The fourth epilogue operand z_prev[i] is loaded with the
+// other three; z_out may alias it too. mpg_csr_jacobi_bound_* is the
+// Gershgorin bound of D A that gives b.
 #include "arnoldi_kernels.hpp"
+#include "mpgmres/solve.h"
+
+#include <cmath>
 
 #include <type_traits>
 
@@ -26,36 +40,71 @@ using namespace mpg;
 
 namespace {
 
-// t = r - s; u = d * t; z + u: each rounded to T
-template <class T>
-__device__ __forceinline__ T sweep_update(T s, T r, T d, T z) {
-#pragma clang fp contract(off)
-    const T t = r - s;
-    const T u = d * t;
-    return z + u;
-}
+// The sweep's epilogue: the Neumann step, the Chebyshev step, and the first
+// Chebyshev step (z_prev = 0: no fourth operand)
+enum : int { kNeumann = 0, kCheb = 1, kChebFirst = 2 };
 
+// what the Chebyshev epilogues take besides the Neumann operands (z_prev
+// carries no __restrict__: z_out may be that vector)
 template <class T>
+struct ChebArgs {
+    const T* z_prev;
+    T alpha, beta;
+};
+
+template <class T, int E>
 struct SweepOps {
     T r, d, z;
 };
+template <class T>
+struct SweepOps<T, kCheb> {
+    T r, d, z, zp;
+};
+
+// row i's epilogue operands (i clamped by the caller)
+template <int E, class T>
+__device__ __forceinline__ SweepOps<T, E> sweep_ops(const T* r, const T* dinv, const T* z_in, const T* z_prev, int i) {
+    if constexpr (E == kCheb) return {r[i], dinv[i], z_in[i], z_prev[i]};
+    else return {r[i], dinv[i], z_in[i]};
+}
+
+// Neumann: t = r - s; u = d * t; z + u. Chebyshev: t, u, then v = beta * u;
+// p = z - z_prev (z for the first step); q = alpha * p; y = z + q; y + v.
+// Each rounded to T.
+template <int E, class T>
+__device__ __forceinline__ T sweep_update(T s, const SweepOps<T, E>& o, T alpha, T beta) {
+#pragma clang fp contract(off)
+    const T t = o.r - s;
+    const T u = o.d * t;
+    if constexpr (E == kNeumann) {
+        return o.z + u;
+    } else {
+        const T v = beta * u;
+        T p = o.z;
+        if constexpr (E == kCheb) p = o.z - o.zp;
+        const T q = alpha * p;
+        const T y = o.z + q;
+        return y + v;
+    }
+}
 
 // (r and z_out carry no __restrict__: they may be one vector)
-template <class T, class A>
+template <class T, class A, int E>
 __global__ __launch_bounds__(kBlock) void k_csr_sweep(const int32_t* __restrict__ blocks, int nblocks,
                                                       const int32_t* __restrict__ rowptr,
                                                       const int32_t* __restrict__ col, const T* __restrict__ val,
                                                       int64_t nnz, const T* __restrict__ dinv, const T* r,
-                                                      const T* __restrict__ z_in, T* z_out) {
+                                                      const T* __restrict__ z_in, T* z_out, ChebArgs<T> ch) {
     __shared__ double prod[kNnzCap];
     __shared__ double scratch[kBlock / kWave];
     for_rows<false, false, A>(
         blocks, nblocks, rowptr, col, val, nnz, [&](int c) { return (double)z_in[c]; },
-        [&](int i) { return SweepOps<T>{r[i], dinv[i], z_in[i]}; },
-        [&](int i, A sum, const SweepOps<T>& o) { z_out[i] = sweep_update((T)sum, o.r, o.d, o.z); }, prod, scratch);
+        [&](int i) { return sweep_ops<E>(r, dinv, z_in, ch.z_prev, i); },
+        [&](int i, A sum, const SweepOps<T, E>& o) { z_out[i] = sweep_update<E>((T)sum, o, ch.alpha, ch.beta); }, prod,
+        scratch);
 }
 
-template <class T, class CI, int W, bool UNI, class A>
+template <class T, class CI, int W, bool UNI, class A, int E>
 __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const int64_t* __restrict__ off,
                                                        const CI* __restrict__ col, const T* __restrict__ val,
                                                        const int32_t* __restrict__ sbase,
@@ -65,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const
                                                        const int32_t* __restrict__ xcol, const T* __restrict__ xval,
                                                        const T* __restrict__ dinv, const T* r,
                                                        const T* __restrict__ z_in, T* z_out, int64_t ustride, int xcd,
-                                                       const int32_t* __restrict__ rows) {
+                                                       const int32_t* __restrict__ rows, ChebArgs<T> ch) {
     const int lane = threadIdx.x & (kWave - 1), wid = wave_id();
     const int s = (xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x) * (kBlock / kWave) + wid;
     if (s >= nslices) return;  // (no workgroup barrier below)
@@ -77,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const
     // the lane's row (a sorted copy's rows[]) and its epilogue operands, issued ahead of the slice
     const int i = rows ? rows[row0 + lane] : row0 + lane;
     const int ic = i < n ? i : 0;
-    const SweepOps<T> o{r[ic], dinv[ic], z_in[ic]};
+    const SweepOps<T, E> o = sweep_ops<E>(r, dinv, z_in, ch.z_prev, ic);
     __builtin_amdgcn_sched_barrier(0);
     row.init_finish(lane, col, val, sbase, pat);
     row.load(0);
@@ -93,21 +142,22 @@ __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const
             row.sum(q, xv, sum);
         }
     }
-    if (i < n) z_out[i] = sweep_update((T)sum, o.r, o.d, o.z);
+    if (i < n) z_out[i] = sweep_update<E>((T)sum, o, ch.alpha, ch.beta);
 }
 
-template <class T, class A>
+template <class T, class A, int E>
 int csr_sweep(mpg_ctx* ctx, const mpg_csr* M, int grid, const T* vals, const T* dinv, const T* r, const T* z_in,
-              T* z_out) {
+              T* z_out, ChebArgs<T> ch = {}) {
     if (M->rows == 0) return MPG_OK;
-    k_csr_sweep<T, A><<<grid, kBlock, 0, ctx->stream>>>(M->blocks, M->nblocks, M->rowptr, M->col, vals, M->nnz, dinv, r,
-                                                        z_in, z_out);
+    k_csr_sweep<T, A, E><<<grid, kBlock, 0, ctx->stream>>>(M->blocks, M->nblocks, M->rowptr, M->col, vals, M->nnz, dinv,
+                                                           r, z_in, z_out, ch);
     MPG_LAUNCH_CHECK(ctx);
     return MPG_OK;
 }
 
-template <class T, class A>
-int sell_sweep(mpg_ctx* ctx, const SellCopy& S, const T* dinv, const T* r, const T* z_in, T* z_out) {
+template <class T, class A, int E>
+int sell_sweep(mpg_ctx* ctx, const SellCopy& S, const T* dinv, const T* r, const T* z_in, T* z_out,
+               ChebArgs<T> ch = {}) {
     if (S.nslices == 0) return MPG_OK;
     const int grid = (S.nslices + kBlock / kWave - 1) / (kBlock / kWave);
     const char* xe = std::getenv("MPG_SELL_XCD");
@@ -120,34 +170,64 @@ int sell_sweep(mpg_ctx* ctx, const SellCopy& S, const T* dinv, const T* r, const
                                                    static_cast<const T*>(S.val), S.sbase, S.spat, S.coff,
                                                    static_cast<const CI*>(S.pat), S.xrp, S.xcol,
                                                    static_cast<const T*>(S.xval), dinv, r, z_in, z_out, S.ustride, xcd,
-                                                   S.rows);
+                                                   S.rows, ch);
             return (int)MPG_OK;
         };
-        return sell_uniform(S) ? go(k_sell_sweep<T, CI, Wc, true, A>) : go(k_sell_sweep<T, CI, Wc, false, A>);
+        return sell_uniform(S) ? go(k_sell_sweep<T, CI, Wc, true, A, E>) : go(k_sell_sweep<T, CI, Wc, false, A, E>);
     });
     if (st) return st;
     MPG_LAUNCH_CHECK(ctx);
     return MPG_OK;
 }
 
+// the Chebyshev step on either storage: the first-step form when there is no z_prev
+template <class T, class A>
+int cheb_sweep(mpg_ctx* ctx, const SellCopy* S, const mpg_csr* M, int grid, const T* vals, const T* dinv, const T* r,
+               const T* z_in, const T* z_prev, T* z_out, T alpha, T beta) {
+    const ChebArgs<T> ch{z_prev, alpha, beta};
+    if (S)
+        return z_prev ? sell_sweep<T, A, kCheb>(ctx, *S, dinv, r, z_in, z_out, ch)
+                      : sell_sweep<T, A, kChebFirst>(ctx, *S, dinv, r, z_in, z_out, ch);
+    return z_prev ? csr_sweep<T, A, kCheb>(ctx, M, grid, vals, dinv, r, z_in, z_out, ch)
+                  : csr_sweep<T, A, kChebFirst>(ctx, M, grid, vals, dinv, r, z_in, z_out, ch);
+}
+
 template <class T>
 int csr_sweep_api(mpg_ctx* ctx, mpg_csr* M, const T* vals, const T* dinv, const T* r, const T* z_in, T* z_out) {
     if (!ctx || !M || M->rows != M->cols || (M->nnz > 0 && !vals)) return MPG_ERR_ARG;
     if (M->rows > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
-    return csr_sweep<T, double>(ctx, M, M->nblocks, vals, dinv, r, z_in, z_out);
+    return csr_sweep<T, double, kNeumann>(ctx, M, M->nblocks, vals, dinv, r, z_in, z_out);
 }
 
 template <class T, int VT>
 int sell_sweep_api(mpg_ctx* ctx, mpg_sell* M, const T* dinv, const T* r, const T* z_in, T* z_out) {
     if (!ctx || !M || M->S.vtype != VT || M->cols != M->S.n) return MPG_ERR_ARG;
     if (M->S.n > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
-    return sell_sweep<T, double>(ctx, M->S, dinv, r, z_in, z_out);
+    return sell_sweep<T, double, kNeumann>(ctx, M->S, dinv, r, z_in, z_out);
 }
 
 template <class T>
-int gdmv_t(mpg_ctx* ctx, int64_t n, const T* d, const T* x, T* y) {
-    if constexpr (std::is_same_v<T, double>) return mpg_gdmv_f64(ctx, n, 1.0, d, x, 0.0, y);
-    else return mpg_gdmv_f32(ctx, n, 1.0f, d, x, 0.0f, y);
+int csr_cheb_api(mpg_ctx* ctx, mpg_csr* M, const T* vals, const T* dinv, const T* r, const T* z_in, const T* z_prev,
+                 T* z_out, T alpha, T beta) {
+    if (!ctx || !M || M->rows != M->cols || (M->nnz > 0 && !vals)) return MPG_ERR_ARG;
+    if (M->rows > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
+    if (M->rows == 0) return MPG_OK;
+    return cheb_sweep<T, double>(ctx, nullptr, M, M->nblocks, vals, dinv, r, z_in, z_prev, z_out, alpha, beta);
+}
+
+template <class T, int VT>
+int sell_cheb_api(mpg_ctx* ctx, mpg_sell* M, const T* dinv, const T* r, const T* z_in, const T* z_prev, T* z_out,
+                  T alpha, T beta) {
+    if (!ctx || !M || M->S.vtype != VT || M->cols != M->S.n) return MPG_ERR_ARG;
+    if (M->S.n > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
+    return cheb_sweep<T, double>(ctx, &M->S, nullptr, 0, static_cast<const T*>(nullptr), dinv, r, z_in, z_prev, z_out,
+                                 alpha, beta);
+}
+
+template <class T>
+int gdmv_t(mpg_ctx* ctx, int64_t n, T alpha, const T* d, const T* x, T* y) {
+    if constexpr (std::is_same_v<T, double>) return mpg_gdmv_f64(ctx, n, alpha, d, x, 0.0, y);
+    else return mpg_gdmv_f32(ctx, n, alpha, d, x, 0.0f, y);
 }
 
 // z_1 = D w (into w for one step, else into work0), then the sweeps between
@@ -157,18 +237,107 @@ int neumann_run(mpg_arnoldi* a, int steps, T* w, T* work0, T* work1) {
     mpg_ctx* ctx = a->ctx;
     const T* d = static_cast<const T*>(a->d.diag);
     const int n = a->d.n;
-    if (int st = gdmv_t<T>(ctx, n, d, w, steps == 1 ? w : work0)) return st;
+    if (int st = gdmv_t<T>(ctx, n, T(1), d, w, steps == 1 ? w : work0)) return st;
     T* bufs[2] = {work0, work1};
     for (int j = 1; j < steps; ++j) {
         const T* z_in = bufs[(j - 1) & 1];
         T* z_out = j == steps - 1 ? w : bufs[j & 1];
         const int st = a->sell.nslices > 0
-                           ? sell_sweep<T, A>(ctx, a->sell, d, w, z_in, z_out)
-                           : csr_sweep<T, A>(ctx, a->d.A, a->Grb, static_cast<const T*>(a->d.val_inner), d, w, z_in,
-                                             z_out);
+                           ? sell_sweep<T, A, kNeumann>(ctx, a->sell, d, w, z_in, z_out)
+                           : csr_sweep<T, A, kNeumann>(ctx, a->d.A, a->Grb, static_cast<const T*>(a->d.val_inner), d,
+                                                       w, z_in, z_out);
         if (st) return st;
     }
     return MPG_OK;
+}
+
+// z_1 = (1 / theta) D w as neumann_run forms D w, then sweep j reads z_j from
+// bufs[(j - 1) & 1] and z_{j-1} from bufs[j & 1] (none at j = 1) and stores
+// z_{j+1} over z_{j-1} (row i's lane alone reads z_{j-1}[i], before its store);
+// the last one stores into w. Two work vectors serve any count.
+template <class T, class A>
+int cheb_run(mpg_arnoldi* a, int steps, double theta, double delta, T* w, T* work0, T* work1) {
+    mpg_ctx* ctx = a->ctx;
+    const T* d = static_cast<const T*>(a->d.diag);
+    const int n = a->d.n;
+    double alpha[64], beta[64];
+    if (int st = mpg_cheb_coeffs(steps, theta, delta, alpha, beta)) return st;
+    if (int st = gdmv_t<T>(ctx, n, (T)alpha[0], d, w, steps == 1 ? w : work0)) return st;
+    T* bufs[2] = {work0, work1};
+    const SellCopy* S = a->sell.nslices > 0 ? &a->sell : nullptr;
+    for (int j = 1; j < steps; ++j) {
+        const T* z_in = bufs[(j - 1) & 1];
+        const T* z_prev = j == 1 ? nullptr : bufs[j & 1];
+        T* z_out = j == steps - 1 ? w : bufs[j & 1];
+        if (int st = cheb_sweep<T, A>(ctx, S, a->d.A, a->Grb, static_cast<const T*>(a->d.val_inner), d, w, z_in, z_prev,
+                                      z_out, (T)alpha[j], (T)beta[j]))
+            return st;
+    }
+    return MPG_OK;
+}
+
+// ---- the Gershgorin bound of D A: max_i |d_i| sum_j |a_ij| ----
+// (a NaN row stays in the maximum: the caller refuses a non-finite bound)
+__device__ __forceinline__ double max_keep_nan(double a, double b) { return (a != a || a > b) ? a : b; }
+
+__device__ __forceinline__ double block_max_keep_nan(double v, double* scratch) {
+    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v = max_keep_nan(v, __shfl_down(v, off, kWave));
+    if (lane == 0) scratch[wid] = v;
+    __syncthreads();
+    double m = scratch[0];
+    for (int q = 1; q < (int)blockDim.x / kWave; ++q) m = max_keep_nan(m, scratch[q]);
+    __syncthreads();
+    return m;  // the same value in every lane
+}
+
+// one lane per row: the fp64 sum of |a_ij| in storage order, times |d_i| in fp64
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_jacobi_bound_rows(int n, const int32_t* __restrict__ rowptr,
+                                                              const T* __restrict__ val, const T* __restrict__ dinv,
+                                                              double* __restrict__ partial) {
+    __shared__ double scratch[kBlock / kWave];
+    double m = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        double sum = 0.0;
+        for (int k = rowptr[i], e = rowptr[i + 1]; k < e; ++k) sum += fabs((double)val[k]);
+        m = max_keep_nan(m, fabs((double)dinv[i]) * sum);
+    }
+    m = block_max_keep_nan(m, scratch);
+    if (threadIdx.x == 0) partial[blockIdx.x] = m;
+}
+
+// the finishing workgroup: the maximum of the partials (any order gives the same value)
+__global__ __launch_bounds__(kMaxRedBlocks) void k_jacobi_bound_finish(int nparts, const double* __restrict__ partial,
+                                                                       double* out) {
+    __shared__ double scratch[kMaxRedBlocks / kWave];
+    const double v = (int)threadIdx.x < nparts ? partial[threadIdx.x] : 0.0;
+    const double m = block_max_keep_nan(v, scratch);
+    if (threadIdx.x == 0) __hip_atomic_store(out, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <class T>
+int jacobi_bound(mpg_ctx* ctx, mpg_csr* M, const T* vals, const T* dinv, double* b_host) {
+    if (!ctx || !M || !b_host || M->rows != M->cols || (M->nnz > 0 && !vals) || (M->rows > 0 && !dinv))
+        return MPG_ERR_ARG;
+    *b_host = 0.0;
+    if (M->rows == 0) return MPG_OK;
+    const int g = grid_for(M->rows, 1, kMaxRedBlocks);
+    k_jacobi_bound_rows<T><<<g, kBlock, 0, ctx->stream>>>(M->rows, M->rowptr, vals, dinv, ctx->red_ws);
+    MPG_LAUNCH_CHECK(ctx);
+    if (ctx->host_ws_dev) {  // into the pinned block, read after the stream has drained
+        k_jacobi_bound_finish<<<1, kMaxRedBlocks, 0, ctx->stream>>>(g, ctx->red_ws,
+                                                                    static_cast<double*>(ctx->host_ws_dev));
+        MPG_LAUNCH_CHECK(ctx);
+        MPG_HIP(ctx, spin_wait(ctx->stream));
+        *b_host = *static_cast<volatile double*>(ctx->host_ws);
+        return MPG_OK;
+    }
+    double* tmp = ctx->red_ws + kMaxRedBlocks * kGemvMaxCols;
+    k_jacobi_bound_finish<<<1, kMaxRedBlocks, 0, ctx->stream>>>(g, ctx->red_ws, tmp);
+    MPG_LAUNCH_CHECK(ctx);
+    return mpg_memcpy_d2h(ctx, b_host, tmp, sizeof(double));
 }
 
 }  // namespace
@@ -192,6 +361,52 @@ int mpg_sell_jacobi_sweep_f32(mpg_ctx_t c, mpg_sell_t A, const float* dinv, cons
     return sell_sweep_api<float, MPG_F32>(c, A, dinv, r, z_in, z_out);
 }
 
+int mpg_csr_cheb_sweep_f64(mpg_ctx_t c, mpg_csr_t A, const double* vals, const double* dinv, const double* r,
+                           const double* z_in, const double* z_prev, double* z_out, double alpha, double beta) {
+    return csr_cheb_api<double>(c, A, vals, dinv, r, z_in, z_prev, z_out, alpha, beta);
+}
+int mpg_csr_cheb_sweep_f32(mpg_ctx_t c, mpg_csr_t A, const float* vals, const float* dinv, const float* r,
+                           const float* z_in, const float* z_prev, float* z_out, float alpha, float beta) {
+    return csr_cheb_api<float>(c, A, vals, dinv, r, z_in, z_prev, z_out, alpha, beta);
+}
+int mpg_sell_cheb_sweep_f64(mpg_ctx_t c, mpg_sell_t A, const double* dinv, const double* r, const double* z_in,
+                            const double* z_prev, double* z_out, double alpha, double beta) {
+    return sell_cheb_api<double, MPG_F64>(c, A, dinv, r, z_in, z_prev, z_out, alpha, beta);
+}
+int mpg_sell_cheb_sweep_f32(mpg_ctx_t c, mpg_sell_t A, const float* dinv, const float* r, const float* z_in,
+                            const float* z_prev, float* z_out, float alpha, float beta) {
+    return sell_cheb_api<float, MPG_F32>(c, A, dinv, r, z_in, z_prev, z_out, alpha, beta);
+}
+
+int mpg_csr_jacobi_bound_f64(mpg_ctx_t c, mpg_csr_t A, const double* vals, const double* dinv, double* b_host) {
+    return jacobi_bound<double>(c, A, vals, dinv, b_host);
+}
+int mpg_csr_jacobi_bound_f32(mpg_ctx_t c, mpg_csr_t A, const float* vals, const float* dinv, double* b_host) {
+    return jacobi_bound<float>(c, A, vals, dinv, b_host);
+}
+
+// (host arithmetic; it lives in this library because mpg_arnoldi_cheb_apply
+// calls it, and the host library, which links this one, hands it on)
+int mpg_cheb_coeffs(int steps, double theta, double delta, double* alpha, double* beta) {
+#pragma clang fp contract(off)
+    if (steps < 1 || steps > 64 || !alpha || !beta || !std::isfinite(theta) || !std::isfinite(delta) || delta <= 0.0 ||
+        theta <= delta)
+        return MPG_ERR_ARG;
+    const double sigma = theta / delta;
+    double rho_prev = 1.0 / sigma;
+    alpha[0] = 1.0 / theta;
+    beta[0] = 0.0;
+    for (int j = 1; j < steps; ++j) {
+        const double two_sigma = 2.0 * sigma;
+        const double rho = 1.0 / (two_sigma - rho_prev);
+        alpha[j] = rho * rho_prev;
+        const double two_rho = 2.0 * rho;
+        beta[j] = two_rho / delta;
+        rho_prev = rho;
+    }
+    return MPG_OK;
+}
+
 int mpg_arnoldi_neumann_apply(mpg_arnoldi_t a, int32_t steps, void* w, void* work0, void* work1) {
     if (!a || !a->ctx || steps < 1 || steps > 64 || !w || (steps >= 2 && !work0) || (steps >= 3 && !work1) ||
         (steps >= 2 && work0 == w) || (steps >= 3 && (work1 == w || work1 == work0)) || !a->d.diag)
@@ -211,3 +426,23 @@ int mpg_arnoldi_neumann_apply(mpg_arnoldi_t a, int32_t steps, void* w, void* wor
 }
 
 }  // extern "C"
+
+extern "C" int mpg_arnoldi_cheb_apply(mpg_arnoldi_t a, int32_t steps, double theta, double delta, void* w, void* work0,
+                                      void* work1) {
+    if (!a || !a->ctx || steps < 1 || steps > 64 || !w || (steps >= 2 && !work0) || (steps >= 3 && !work1) ||
+        (steps >= 2 && work0 == w) || (steps >= 3 && (work1 == w || work1 == work0)) || !a->d.diag ||
+        !std::isfinite(theta) || !std::isfinite(delta) || delta <= 0.0 || theta <= delta)
+        return MPG_ERR_ARG;
+    // (mpg_arnoldi_neumann_apply's combinations)
+    if ((a->combo != 0 && a->combo != 2 && a->combo != 3) || a->front != 0 || a->d.n_ext != a->d.n)
+        return MPG_ERR_UNSUPPORTED;
+    if (a->d.n == 0) return MPG_OK;
+    if (a->combo == 0)
+        return cheb_run<double, double>(a, steps, theta, delta, static_cast<double*>(w), static_cast<double*>(work0),
+                                        static_cast<double*>(work1));
+    if (a->acc32)
+        return cheb_run<float, float>(a, steps, theta, delta, static_cast<float*>(w), static_cast<float*>(work0),
+                                      static_cast<float*>(work1));
+    return cheb_run<float, double>(a, steps, theta, delta, static_cast<float*>(w), static_cast<float*>(work0),
+                                   static_cast<float*>(work1));
+}

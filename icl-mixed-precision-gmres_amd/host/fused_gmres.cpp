@@ -148,7 +148,13 @@ struct FusedEngine::Impl {
     int nm_steps = 0;   // sweeps applied between the phase kernels; 0: none (another preconditioner, or one sweep)
     int nm_asked = 0;   // jacobi_steps of prec neumann; 0: another preconditioner
     DevMem nm_work0, nm_work1;
-    bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || nm_asked == 1; }
+    // Chebyshev polynomial (prec chebyshev): the same slot, vectors and counts
+    // (nm_steps = nm_asked for every count: one step is Jacobi scaled by
+    // 1 / theta, not jacobi's bits), through mpg_arnoldi_cheb_apply on the
+    // interval read at set-up
+    bool cheb = false;
+    ChebInterval cheb_iv{};
+    bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || (nm_asked == 1 && !cheb); }
     bool orthloss = false;    // LostOrthogonality: v_{k+1} stored each step, S / u below
     DevMem loss_S, loss_u;    // (m+1) x (m+1) and m+2 of T, zero-filled (IterUtil.hpp:185-191)
 
@@ -195,6 +201,10 @@ struct FusedEngine::Impl {
     // Jacobi, the Jacobi sweeps, or ILU with typesafe_apply's casts when the preconditioner
     // precision differs (gmres.cpp:12-22)
     void apply_neumann(void* w) {
+        if (cheb)
+            return check(mpg_arnoldi_cheb_apply(arn, nm_steps, cheb_iv.theta(), cheb_iv.delta(), w, nm_work0.p,
+                                                nm_work1.p),
+                         "Chebyshev apply", ctx);
         check(mpg_arnoldi_neumann_apply(arn, nm_steps, w, nm_work0.p, nm_work1.p), "Jacobi-sweep apply", ctx);
     }
     void apply_ilu(void* w) {
@@ -307,8 +317,8 @@ void FusedEngine::Impl::resolve_policy() {
     if (int st = plan_cycle(P, cycle))
         throw StatusError(st, "MPG_STEP_DOTS=2 / MPG_FUSE_DOTS=2: a step of the cycle cannot take the required SpMV + "
                               "dots launch (one GPU, plain CGS with in-launch sums, no preconditioner launch -- ILU, "
-                              "block Jacobi, Jacobi sweeps -- between the SpMV and the dots, storage the launch "
-                              "supports)");
+                              "block Jacobi, Jacobi or Chebyshev sweeps -- between the SpMV and the dots, storage the "
+                              "launch supports)");
 }
 
 FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int n_ext, int n_front)
@@ -330,18 +340,21 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     if (ilu && comm)
         throw std::invalid_argument("ILU / ILU-Jacobi factor the whole matrix: not available on a row-partitioned solve");
     const bool bjacobi = a.prec == MPG_PREC_BLOCK_JACOBI;
-    const bool neumann = a.prec == MPG_PREC_NEUMANN;
+    const bool chebyshev = a.prec == MPG_PREC_CHEBYSHEV;
+    const bool neumann = a.prec == MPG_PREC_NEUMANN || chebyshev;  // (the sweeps' set-up, whichever polynomial)
     if (!ilu && !bjacobi && !neumann && a.prec != MPG_PREC_IDENTITY && a.prec != MPG_PREC_JACOBI)
         throw std::invalid_argument("Unknown prec type");
     if (neumann) {
-        check_neumann_args(a);
+        chebyshev ? check_cheb_args(a) : check_neumann_args(a);
         if (comm)
             throw StatusError(MPG_ERR_UNSUPPORTED,
-                              "prec neumann is not available on a row-partitioned solve: every sweep needs a halo "
-                              "exchange of z (the follow-up that would make it the first preconditioner stronger than "
-                              "Jacobi on more than one GPU)");
+                              std::string("prec ") + (chebyshev ? "chebyshev" : "neumann") +
+                                  " is not available on a row-partitioned solve: every sweep needs a halo "
+                                  "exchange of z (the follow-up that would make it the first preconditioner stronger "
+                                  "than Jacobi on more than one GPU)");
+        I.cheb = chebyshev;
         I.nm_asked = a.jacobi_steps;
-        I.nm_steps = a.jacobi_steps > 1 ? a.jacobi_steps : 0;
+        I.nm_steps = a.jacobi_steps > 1 || chebyshev ? a.jacobi_steps : 0;
     }
     if (bjacobi) {
         const int bs = a.prec_block == 0 ? 3 : a.prec_block;
@@ -432,6 +445,21 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
             check(mpg_jacobi_diag_f32(ctx, I.csr, f32.as<float>(), rowmax, I.diag.as<float>()), "jacobi", ctx);
             check(mpg_ctx_sync(ctx), "sync", ctx);
         }
+    }
+
+    if (I.cheb) {
+        // the interval, from the Gershgorin bound of D A on the matrix the sweeps run on (P = T = its value type)
+        I.cheb_iv = cheb_interval([&] {
+            double bound = 0.0;
+            check(ty.P == MPG_F64 ? mpg_csr_jacobi_bound_f64(ctx, I.csr, static_cast<const double*>(I.val_inner),
+                                                             I.diag.as<double>(), &bound)
+                                  : mpg_csr_jacobi_bound_f32(ctx, I.csr, static_cast<const float*>(I.val_inner),
+                                                             I.diag.as<float>(), &bound),
+                  "Gershgorin bound", ctx);
+            return bound;
+        });
+        double al[64], be[64];
+        cheb_coefficients(I.nm_steps, I.cheb_iv, al, be);  // (refused here, not at the first application)
     }
 
     // block Jacobi in the preconditioner precision, from the matrix Jacobi<P>
@@ -974,8 +1002,11 @@ double FusedEngine::phase_bytes(int which) const {
     const double jac = I.jacobi_inside() ? 1.0 : I.bj_bs ? (bjf ? 0.0 : 2 * sT / sP) + I.bj_bs : 0.0;
     // the Jacobi sweeps' launches after the SpMV: the gdmv (w read, z written,
     // the diagonal), then per sweep the matrix again, z read and written and
-    // three more n-vectors (r, the diagonal, z's own entry)
-    const double nm = I.nm_steps ? (2 * sT + sP) * n + (I.nm_steps - 1) * (z * (sV + 4) + (n + 1) * 4 + 5 * n * sT) : 0.0;
+    // three more n-vectors (r, the diagonal, z's own entry); a Chebyshev sweep
+    // after the first reads z_prev too
+    const double nm = I.nm_steps ? (2 * sT + sP) * n + (I.nm_steps - 1) * (z * (sV + 4) + (n + 1) * 4 + 5 * n * sT) +
+                                       (I.cheb && I.nm_steps > 2 ? (I.nm_steps - 2) * n * sT : 0.0)
+                                 : 0.0;
     if (which == 0) {
         // SURVEY §8(d) B_spmv, the same for every storage: CSR values + int32
         // columns + row pointers, x read once, y written (the SELL-64 copy
@@ -1020,6 +1051,12 @@ mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
 int FusedEngine::prec_fused() const { return p_->bj_bs ? (p_->bj_fused_step ? 1 : 0) : -1; }
 int FusedEngine::prec_sweeps() const { return p_->nm_asked ? p_->nm_asked : -1; }
+bool FusedEngine::prec_interval(double* a, double* b) const {
+    if (!p_->cheb) return false;
+    if (a) *a = p_->cheb_iv.a;
+    if (b) *b = p_->cheb_iv.b;
+    return true;
+}
 int FusedEngine::step_dots_steps() const {
     return (int)std::count_if(p_->cycle.begin(), p_->cycle.end(), [](const Op& o) { return o.kind == OpKind::StepDots; });
 }
@@ -1154,6 +1191,9 @@ int mpg_engine_sell_columns(mpg_engine_t e, int32_t* form, int64_t* csr_slices, 
 
 int mpg_engine_prec_fused(mpg_engine_t e) { return e && e->eng ? e->eng->prec_fused() : -1; }
 int mpg_engine_prec_sweeps(mpg_engine_t e) { return e && e->eng ? e->eng->prec_sweeps() : -1; }
+int mpg_engine_prec_interval(mpg_engine_t e, double* a, double* b) {
+    return e && e->eng && e->eng->prec_interval(a, b) ? 0 : -1;
+}
 int mpg_engine_accum(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return mpg_arnoldi_accum(e->eng->arnoldi());

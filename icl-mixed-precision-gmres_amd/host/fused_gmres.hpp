@@ -29,23 +29,26 @@
 
 namespace mpg {
 
-// prec neumann (MPG_PREC_NEUMANN): the sweep count and the modes it runs in,
+// prec neumann and prec chebyshev (MPG_PREC_NEUMANN, MPG_PREC_CHEBYSHEV; `name`
+// in the messages): the sweep count and the modes they run in,
 // checked by both engines before any set-up. The sweeps run in the Arnoldi
 // precision on the Arnoldi matrix, so the preconditioner precision has to be
 // that precision (not mode single-prec) and the matrix has to exist in it
 // (not mode mixed-half, whose inner operator is the fp16 copy).
-inline void check_neumann_args(const mpg_solve_args& a) {
+inline void check_sweep_prec_args(const mpg_solve_args& a, const std::string& name) {
     if (a.jacobi_steps < 1 || a.jacobi_steps > 64)
-        throw std::invalid_argument("prec neumann: jacobi_steps = " + std::to_string(a.jacobi_steps) +
+        throw std::invalid_argument("prec " + name + ": jacobi_steps = " + std::to_string(a.jacobi_steps) +
                                     " is outside [1, 64]");
     if (a.mode == MPG_MODE_SINGLE_PREC)
         throw StatusError(MPG_ERR_UNSUPPORTED,
-                          "prec neumann is not available in mode single-prec: the sweeps run in the Arnoldi "
+                          "prec " + name + " is not available in mode single-prec: the sweeps run in the Arnoldi "
                           "precision and would need A in a second precision");
     if (a.mode == MPG_MODE_MIXED_HALF)
-        throw StatusError(MPG_ERR_UNSUPPORTED,
-                          "prec neumann is not available in mode mixed-half: the inner operator is the fp16 copy of A");
+        throw StatusError(MPG_ERR_UNSUPPORTED, "prec " + name + " is not available in mode mixed-half: the inner "
+                                               "operator is the fp16 copy of A");
 }
+inline void check_neumann_args(const mpg_solve_args& a) { check_sweep_prec_args(a, "neumann"); }
+inline void check_cheb_args(const mpg_solve_args& a) { check_sweep_prec_args(a, "chebyshev"); }
 
 // Communication seam of the row-partitioned solve: a single-GPU engine has
 // no communicator; a multi-GPU rank supplies one (see comm.hpp).
@@ -146,6 +149,7 @@ public:
     const int64_t* half_stats() const;
     int prec_fused() const;  // mpg_engine_prec_fused
     int prec_sweeps() const;  // mpg_engine_prec_sweeps
+    bool prec_interval(double* a, double* b) const;  // mpg_engine_prec_interval
     int cgs_stream_steps() const;      // CGS update launches of a cycle that take the streaming form
     int step_dots_steps() const;       // steps of a cycle that run the SpMV inside the dots' launch
     bool givens_rider() const;         // ... and one of them folds the Givens step (k_step_dots' rider workgroup)

@@ -14,7 +14,11 @@
 // --prec bjacobi [--prec-block {2,3,4}] (the inverse of each node's diagonal
 // block; 3 unknowns per node unless told), --prec neumann [--jacobi-steps S]
 // (S Jacobi sweeps on A z = r from z = 0, the truncated Neumann series;
-// 1 <= S <= 64, S = 1 is --prec jacobi), --device D, --stop-on-breakdown (end the solve with an error at the first
+// 1 <= S <= 64, S = 1 is --prec jacobi), --prec chebyshev [--jacobi-steps S]
+// [--cheb-ratio R] [--cheb-lmax L] (the Chebyshev polynomial of S sweeps for a
+// spectrum of D A near [b / R, b]: R > 1, default 30; b = L > 0, default the
+// Gershgorin bound; the two flags set MPG_CHEB_RATIO / MPG_CHEB_LMAX for this
+// process), --device D, --stop-on-breakdown (end the solve with an error at the first
 // non-finite Arnoldi residual; without it the count goes to stderr),
 // --ngpus N (row-partition the fused solve over N GPUs of this process, one
 // host thread per GPU, RCCL clique by ncclCommInitAll: mpg_solve_multi_gpu;
@@ -79,6 +83,8 @@ int main(int argc, char* argv[]) {
         else if (f == "--rand") rand_seed = (unsigned)std::stoi(next());
         else if (f == "--jacobi-steps") a.jacobi_steps = std::stoi(next());
         else if (f == "--prec-block") a.prec_block = std::stoi(next());
+        else if (f == "--cheb-ratio") setenv("MPG_CHEB_RATIO", next(), 1);
+        else if (f == "--cheb-lmax") setenv("MPG_CHEB_LMAX", next(), 1);
         else if (f == "--gpu") { /* always on the GPU */ }
         else if (f == "--device") a.device = std::stoi(next());
         else if (f == "--ngpus") ngpus = std::stoi(next());
@@ -112,6 +118,7 @@ int main(int argc, char* argv[]) {
             else if (v == "ilu_jacobi") a.prec = MPG_PREC_ILU_JACOBI;
             else if (v == "bjacobi") a.prec = MPG_PREC_BLOCK_JACOBI;
             else if (v == "neumann") a.prec = MPG_PREC_NEUMANN;
+            else if (v == "chebyshev") a.prec = MPG_PREC_CHEBYSHEV;
             else { std::cout << "Unknown Preconditioner" << std::endl; return 1; }
         } else if (f == "--engine") {
             const std::string v = next();

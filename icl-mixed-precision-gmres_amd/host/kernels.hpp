@@ -16,6 +16,7 @@
 #define MPGMRES_KERNELS_HPP
 
 #include <cassert>
+#include <functional>
 
 #include "types.hpp"
 
@@ -217,6 +218,71 @@ public:
         gdmv(1.0, diag_, rhs, 0.0, steps_ == 1 ? rhs : work0_);
         for (int j = 1; j < steps_; ++j)
             jacobi_sweep(A_, diag_, rhs, (j - 1) & 1 ? work1_ : work0_, j == steps_ - 1 ? rhs : (j & 1 ? work1_ : work0_));
+    }
+};
+
+// backend primitives of the Chebyshev preconditioner: one sweep
+// z_out = z_in + alpha (z_in - z_prev) + beta dinv (r - A z_in), seven
+// operations each rounded to Type (an empty z_prev: the first sweep, z_prev =
+// 0); z_out may be r or z_prev, never z_in. And the Gershgorin bound
+// max_i |dinv_i| sum_j |a_ij| of dinv A, a host value (set-up only).
+template <class Type, class Device>
+void cheb_sweep(SparseMatrix<Type, Device> A, Vect<Type, Device> dinv, Vect<Type, Device> r, Vect<Type, Device> z_in,
+                Vect<Type, Device> z_prev, Vect<Type, Device> z_out, Type alpha, Type beta);
+template <class Type, class Device>
+double jacobi_bound(SparseMatrix<Type, Device> A, Vect<Type, Device> dinv);
+
+// The interval [b / ratio, b] of the Chebyshev preconditioner, from the two
+// settings read when it is set up: b = MPG_CHEB_LMAX (a real > 0) or, without
+// it, gershgorin(); ratio = MPG_CHEB_RATIO (a real > 1), 30 without it. Throws
+// (a status error naming the value) for a setting outside its range or a
+// bound that is not finite and positive. Defined by the backend.
+struct ChebInterval {
+    double a, b;
+    double theta() const { return 0.5 * (a + b); }
+    double delta() const { return 0.5 * (b - a); }
+};
+ChebInterval cheb_interval(const std::function<double()>& gershgorin);
+// mpg_cheb_coeffs (solve.h) for that interval; throws where it refuses
+void cheb_coefficients(int steps, const ChebInterval& iv, double* alpha, double* beta);
+
+// Chebyshev polynomial preconditioner (an addition to the reference's set):
+// z_steps of the Chebyshev iteration on A z = r from z = 0 for a spectrum of
+// D A near [a, b], D Jacobi's inverse diagonal of A_diag, the sweeps on A (as
+// Neumann above). z_1 = (1 / theta) D r; steps = 1 is Jacobi scaled by
+// 1 / theta. The coefficients are host constants rounded once to Type, so
+// apply reads nothing on the host.
+template <class Type, class Device>
+class Chebyshev : public LinearOperator<Type, Device> {
+    SparseMatrix<Type, Device> A_;
+    int steps_;
+    Vect<Type, Device> diag_, work0_, work1_;
+    ChebInterval iv_{};
+    double alpha_[64], beta_[64];
+
+public:
+    Chebyshev(SparseMatrix<Type, Device> A_diag, SparseMatrix<Type, Device> A, int steps)
+        : A_(A), steps_(steps), diag_(A.nrows()) {
+        jacobi_diag(A_diag, diag_);
+        iv_ = cheb_interval([&] { return jacobi_bound(A_, diag_); });
+        cheb_coefficients(steps_, iv_, alpha_, beta_);
+        if (steps >= 2) work0_ = Vect<Type, Device>(A.nrows());
+        if (steps >= 3) work1_ = Vect<Type, Device>(A.nrows());
+    }
+    int n() const { return (int)diag_.n(); }
+    int steps() const { return steps_; }
+    ChebInterval interval() const { return iv_; }
+    Vect<Type, Device> diag_vect() { return diag_; }
+    // z_1 into work0 (in place for one step); sweep j reads z_j from
+    // buf[(j - 1) & 1] and z_{j-1} from buf[j & 1] and stores over the
+    // latter, the last one into rhs
+    void apply(Vect<Type, Device> rhs) override {
+        gdmv(Type(alpha_[0]), diag_, rhs, Type(0), steps_ == 1 ? rhs : work0_);
+        for (int j = 1; j < steps_; ++j) {
+            Vect<Type, Device> keep = j & 1 ? work1_ : work0_;
+            cheb_sweep(A_, diag_, rhs, (j - 1) & 1 ? work1_ : work0_, j == 1 ? Vect<Type, Device>() : keep,
+                       j == steps_ - 1 ? rhs : keep, Type(alpha_[j]), Type(beta_[j]));
+        }
     }
 };
 

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <sstream>
@@ -1166,6 +1167,81 @@ template <> void jacobi_sweep<float, Hip>(SparseMatrix<float, Hip> A, Vect<float
     check(s ? mpg_sell_jacobi_sweep_f32(C, s, d.data(), r.data(), zi.data(), zo.data())
             : mpg_csr_jacobi_sweep_f32(C, A.csr(), A.vals_data(), d.data(), r.data(), zi.data(), zo.data()),
           "Jacobi sweep");
+}
+
+// one Chebyshev sweep and the Gershgorin bound of D A, on the storage
+// jacobi_sweep takes (the bound reads the CSR arrays every copy keeps)
+template <> void cheb_sweep<double, Hip>(SparseMatrix<double, Hip> A, Vect<double, Hip> d, Vect<double, Hip> r,
+                                         Vect<double, Hip> zi, Vect<double, Hip> zp, Vect<double, Hip> zo, double alpha,
+                                         double beta) {
+    assert(A.nrows() == A.ncols() && !A.is_transposed() && (size_t)A.nrows() == r.n() && d.n() == r.n() &&
+           zi.n() == r.n() && zo.n() == r.n() && (zp.n() == 0 || zp.n() == r.n()));
+    mpg_sell_t s = A.node() ? nullptr : A.sell();
+    check(s ? mpg_sell_cheb_sweep_f64(C, s, d.data(), r.data(), zi.data(), zp.data(), zo.data(), alpha, beta)
+            : mpg_csr_cheb_sweep_f64(C, A.csr(), A.vals_data(), d.data(), r.data(), zi.data(), zp.data(), zo.data(),
+                                     alpha, beta),
+          "Chebyshev sweep");
+}
+template <> void cheb_sweep<float, Hip>(SparseMatrix<float, Hip> A, Vect<float, Hip> d, Vect<float, Hip> r,
+                                        Vect<float, Hip> zi, Vect<float, Hip> zp, Vect<float, Hip> zo, float alpha,
+                                        float beta) {
+    assert(A.nrows() == A.ncols() && !A.is_transposed() && (size_t)A.nrows() == r.n() && d.n() == r.n() &&
+           zi.n() == r.n() && zo.n() == r.n() && (zp.n() == 0 || zp.n() == r.n()));
+    mpg_sell_t s = A.node() ? nullptr : A.sell();
+    check(s ? mpg_sell_cheb_sweep_f32(C, s, d.data(), r.data(), zi.data(), zp.data(), zo.data(), alpha, beta)
+            : mpg_csr_cheb_sweep_f32(C, A.csr(), A.vals_data(), d.data(), r.data(), zi.data(), zp.data(), zo.data(),
+                                     alpha, beta),
+          "Chebyshev sweep");
+}
+template <> double jacobi_bound<double, Hip>(SparseMatrix<double, Hip> A, Vect<double, Hip> d) {
+    double b = 0.0;
+    check(mpg_csr_jacobi_bound_f64(C, A.csr(), A.vals_data(), d.data(), &b), "Gershgorin bound");
+    return b;
+}
+template <> double jacobi_bound<float, Hip>(SparseMatrix<float, Hip> A, Vect<float, Hip> d) {
+    double b = 0.0;
+    check(mpg_csr_jacobi_bound_f32(C, A.csr(), A.vals_data(), d.data(), &b), "Gershgorin bound");
+    return b;
+}
+
+namespace {
+// a setting that holds one real: true and the value when it is set
+bool real_setting(const char* name, double& v, std::string& text) {
+    const char* e = std::getenv(name);
+    if (!e || !*e) return false;
+    text = e;
+    char* end = nullptr;
+    v = std::strtod(e, &end);
+    if (end == e || *end) v = std::nan("");
+    return true;
+}
+}  // namespace
+
+ChebInterval cheb_interval(const std::function<double()>& gershgorin) {
+    double ratio = 30.0, b = 0.0;
+    std::string text;
+    if (real_setting("MPG_CHEB_RATIO", ratio, text) && !(std::isfinite(ratio) && ratio > 1.0))
+        throw mpg::StatusError(MPG_ERR_ARG, "prec chebyshev: MPG_CHEB_RATIO = " + text + " is not a real > 1");
+    if (real_setting("MPG_CHEB_LMAX", b, text)) {
+        if (!(std::isfinite(b) && b > 0.0))
+            throw mpg::StatusError(MPG_ERR_ARG, "prec chebyshev: MPG_CHEB_LMAX = " + text + " is not a real > 0");
+    } else {
+        b = gershgorin();
+        if (!(std::isfinite(b) && b > 0.0)) {
+            std::ostringstream os;
+            os << "prec chebyshev: the Gershgorin bound of D A is " << b << ", not a finite positive value";
+            throw mpg::StatusError(MPG_ERR_BREAKDOWN, os.str());
+        }
+    }
+    return ChebInterval{b / ratio, b};
+}
+
+void cheb_coefficients(int steps, const ChebInterval& iv, double* alpha, double* beta) {
+    if (int st = mpg_cheb_coeffs(steps, iv.theta(), iv.delta(), alpha, beta)) {
+        std::ostringstream os;
+        os << "prec chebyshev: no coefficients for " << steps << " steps on [" << iv.a << ", " << iv.b << "]";
+        throw mpg::StatusError(st, os.str());
+    }
 }
 
 // ---- ILU(0) / ILU-Jacobi (kernels_mkl.cpp:355-506, kernels_cuda.cpp:617-791) ----

@@ -106,6 +106,19 @@ int mpg_arnoldi_prec_fused(mpg_arnoldi_t a, int which);
  * diagonal; MPG_ERR_UNSUPPORTED: a preconditioner precision or value type
  * other than T (single-prec, mixed-half), or a workspace with halo rows. */
 int mpg_arnoldi_neumann_apply(mpg_arnoldi_t a, int32_t steps, void* w, void* work0, void* work1);
+/* The Chebyshev polynomial preconditioner (MPG_PREC_CHEBYSHEV, solve.h; an
+ * addition to the reference's set) on the workspace's own Arnoldi matrix, set
+ * up like mpg_arnoldi_neumann_apply's: w <- z_steps of the recurrence on the
+ * interval [theta - delta, theta + delta]. The coefficients come from
+ * mpg_cheb_coeffs(steps, theta, delta, ., .), each rounded once to T.
+ * mpg_gdmv_*(alpha_0, D, w, 0, .) forms z_1 (in place for steps == 1), then
+ * sweep j = 1 .. steps - 1 of mpg_*_cheb_sweep_*'s arithmetic (capi.h) in the
+ * workspace's accumulation class reads z_in = buf[(j - 1) & 1] and z_prev =
+ * buf[j & 1] (none at j = 1) and stores into buf[j & 1], the last one into w;
+ * buf = {work0, work1}. Vectors, launches and MPG_ERR_UNSUPPORTED as for
+ * mpg_arnoldi_neumann_apply; MPG_ERR_ARG also unless 0 < delta < theta, finite. */
+int mpg_arnoldi_cheb_apply(mpg_arnoldi_t a, int32_t steps, double theta, double delta, void* w, void* work0,
+                           void* work1);
 
 /* Storage the Arnoldi SpMV runs on: *format 1 = CSR row blocks (cuSPARSE
  * csrmv's input, types_cuda.hpp:53-60), 2 = SELL-64 copy made at create

@@ -476,6 +476,34 @@ int mpg_sell_jacobi_sweep_f64(mpg_ctx_t ctx, mpg_sell_t A, const double* dinv, c
 int mpg_sell_jacobi_sweep_f32(mpg_ctx_t ctx, mpg_sell_t A, const float* dinv, const float* r, const float* z_in,
                               float* z_out);
 
+/* ---- Chebyshev sweep (neumann.hip; an addition to the reference's set): one
+ * step of the Chebyshev polynomial preconditioner (MPG_PREC_CHEBYSHEV, solve.h)
+ *   z_{j+1} = z_j + alpha (z_j - z_{j-1}) + beta D (r - A z_j)
+ * on a square matrix, alpha and beta from mpg_cheb_coeffs (solve.h) rounded to
+ * T (z_1 = alpha_0 D r is mpg_gdmv_*(alpha_0, dinv, r, 0, z)). Per row i:
+ *   s_i = T(sum_j a_ij z_in[j])   the row sum of mpg_*_jacobi_sweep_* above
+ *   t = r[i] - s_i;  u = dinv[i] * t;  v = beta * u
+ *   p = z_in[i] - z_prev[i];  q = alpha * p;  y = z_in[i] + q;  z_out[i] = y + v
+ * each of the seven rounded to T (no contraction). z_prev == NULL is the first
+ * step (z_0 = 0): p = z_in[i]. z_out may be r or z_prev (row i's lane alone
+ * reads either, before its store); z_out == z_in is MPG_ERR_ARG. One launch;
+ * MPG_ERR_ARG as for the Jacobi sweep. */
+int mpg_csr_cheb_sweep_f64(mpg_ctx_t ctx, mpg_csr_t A, const double* vals, const double* dinv, const double* r,
+                           const double* z_in, const double* z_prev, double* z_out, double alpha, double beta);
+int mpg_csr_cheb_sweep_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, const float* dinv, const float* r,
+                           const float* z_in, const float* z_prev, float* z_out, float alpha, float beta);
+int mpg_sell_cheb_sweep_f64(mpg_ctx_t ctx, mpg_sell_t A, const double* dinv, const double* r, const double* z_in,
+                            const double* z_prev, double* z_out, double alpha, double beta);
+int mpg_sell_cheb_sweep_f32(mpg_ctx_t ctx, mpg_sell_t A, const float* dinv, const float* r, const float* z_in,
+                            const float* z_prev, float* z_out, float alpha, float beta);
+/* The Gershgorin bound of D A (an addition to the reference's set):
+ * *b_host = max_i |dinv[i]| * sum_j |a_ij|, each row's sum in fp64 in storage
+ * order, the product in fp64; a maximum over per-workgroup partials, so the
+ * same bits on every call. A NaN row gives NaN. Set-up only: it waits for the
+ * context's stream. MPG_ERR_ARG for a non-square matrix or a NULL argument. */
+int mpg_csr_jacobi_bound_f64(mpg_ctx_t ctx, mpg_csr_t A, const double* vals, const double* dinv, double* b_host);
+int mpg_csr_jacobi_bound_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, const float* dinv, double* b_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,9 +38,15 @@ typedef enum {
     MPG_PREC_JACOBI = 2,
     MPG_PREC_IDENTITY = 3,
     MPG_PREC_BLOCK_JACOBI = 4, /* new: the inverse of each node's diagonal block (mpg_bjacobi_*, capi.h) */
-    MPG_PREC_NEUMANN = 5 /* new: jacobi_steps Jacobi sweeps on A z = r from z = 0, the truncated Neumann series
-                            sum_{j<s} (I - D A)^j D with Jacobi's D (mpg_*_jacobi_sweep_*, capi.h); s = 1 is
-                            MPG_PREC_JACOBI's bits */
+    MPG_PREC_NEUMANN = 5, /* new: jacobi_steps Jacobi sweeps on A z = r from z = 0, the truncated Neumann series
+                             sum_{j<s} (I - D A)^j D with Jacobi's D (mpg_*_jacobi_sweep_*, capi.h); s = 1 is
+                             MPG_PREC_JACOBI's bits */
+    MPG_PREC_CHEBYSHEV = 6 /* new: the Chebyshev polynomial of degree jacobi_steps - 1 in D A applied to D r, for a
+                              spectrum of D A near [b / ratio, b] (mpg_*_cheb_sweep_*, capi.h; mpg_cheb_coeffs and
+                              mpg_engine_prec_interval below). b: the Gershgorin bound of D A, or MPG_CHEB_LMAX
+                              (a real > 0); ratio: MPG_CHEB_RATIO (a real > 1, default 30); both read once when the
+                              preconditioner is set up. For spectra on the positive real axis: a banded matrix whose
+                              D A has a disc around 1 wants a small ratio, or MPG_PREC_NEUMANN */
 } mpg_prec_t;
 
 typedef enum {
@@ -66,8 +72,8 @@ typedef struct {
     double rtol;           /* --rtol (0: base Convergence) */
     int32_t repeat_iter;   /* --repeat-iter */
     int32_t orthloss;      /* --orthloss */
-    int32_t jacobi_steps;  /* --jacobi-steps: sweeps of MPG_PREC_ILU_JACOBI's solves; MPG_PREC_NEUMANN's sweep
-                              count s, 1 <= s <= 64 (anything else MPG_ERR_ARG) */
+    int32_t jacobi_steps;  /* --jacobi-steps: sweeps of MPG_PREC_ILU_JACOBI's solves; MPG_PREC_NEUMANN's and
+                              MPG_PREC_CHEBYSHEV's sweep count s, 1 <= s <= 64 (anything else MPG_ERR_ARG) */
     int32_t verbose;       /* print the reference's stdout lines */
     int32_t device;        /* HIP device (mpg_solve only) */
     int32_t threads;       /* host threads (oracle only; 0 = default) */
@@ -207,9 +213,21 @@ int mpg_engine_cgs_stream_steps(mpg_engine_t e);
 /* block Jacobi: 1 when the apply runs inside the SpMV / residual launches, 0 when it is a
  * launch of its own between them and the dots; -1 for every other preconditioner */
 int mpg_engine_prec_fused(mpg_engine_t e);
-/* MPG_PREC_NEUMANN: the sweep count the engine applies per preconditioner application (jacobi_steps:
- * one gdmv launch and that many minus one sweep launches); -1 for every other preconditioner */
+/* MPG_PREC_NEUMANN, MPG_PREC_CHEBYSHEV: the sweep count the engine applies per preconditioner application
+ * (jacobi_steps: one gdmv launch and that many minus one sweep launches); -1 for every other preconditioner */
 int mpg_engine_prec_sweeps(mpg_engine_t e);
+/* MPG_PREC_CHEBYSHEV (an addition to the reference's set): the interval [*a, *b] the engine built its
+ * coefficients for; returns 0, or -1 for every other preconditioner (a and b untouched) */
+int mpg_engine_prec_interval(mpg_engine_t e, double* a, double* b);
+/* The Chebyshev preconditioner's coefficients (an addition to the reference's set) for `steps` sweeps on the
+ * interval [theta - delta, theta + delta], 0 < delta < theta: with sigma = theta / delta and rho_0 = 1 / sigma,
+ *   alpha[0] = 1 / theta (z_1 = alpha[0] D r), beta[0] = 0, and for j = 1 .. steps - 1
+ *   rho_j = 1 / (2 sigma - rho_{j-1});  alpha[j] = rho_j rho_{j-1};  beta[j] = 2 rho_j / delta
+ * in fp64, in that operation order, without contraction; sweep j is
+ *   z_{j+1} = z_j + alpha[j] (z_j - z_{j-1}) + beta[j] D (r - A z_j),  z_0 = 0.
+ * alpha, beta: `steps` entries each. Both engines call it and round each value once to the vectors' type.
+ * MPG_ERR_ARG: steps outside [1, 64], a NULL array, or not 0 < delta < theta (finite). Host arithmetic only. */
+int mpg_cheb_coeffs(int steps, double theta, double delta, double* alpha, double* beta);
 /* the accumulation class the engine's Arnoldi runs: MPG_ACCUM_F64 0 / MPG_ACCUM_F32 1 (arnoldi.h) */
 int mpg_engine_accum(mpg_engine_t e);
 /* the residual prologue's storage (mpg_arnoldi_prologue_format: 1 CSR, 2 SELL, 3 node blocks) */
@@ -244,7 +262,7 @@ typedef struct {
     int32_t step_dots;    /* MPG_STEP_DOTS: 0 never, 1 wherever supported, 2 required, -1 the steps lo <= k + 1 <= hi */
     int32_t step_dots_lo, step_dots_hi;
     int32_t sep_prec;          /* a preconditioner that is not applied inside the phase kernels (ILU, block Jacobi,
-                                  the Jacobi-sweep polynomial) */
+                                  the Jacobi-sweep and Chebyshev polynomials) */
     int32_t sep_prec_step;     /* ... a launch of its own after every SpMV */
     int32_t sep_prec_prologue; /* ... and after the residual prologue */
     int32_t partials_max_cols; /* mpg_arnoldi_partials_max_cols() */

@@ -1,6 +1,6 @@
 """GMRES it/s with each preconditioner on one MI355X (fused engine, mixed
 CGS GMRES(m), tol = 0, fixed work): identity, Jacobi, the Jacobi-sweep
-polynomial (neumann, 2 and 4 sweeps), ILU(0) (sync-free triangular solves) and
+polynomial (neumann, 2 and 4 sweeps; chebyshev:2/3/4/6 on request), ILU(0) (sync-free triangular solves) and
 ILU-Jacobi (5 sweeps), on LAP-1M (the 100^3 7-point Laplacian,
 triangular-solve depth ~ 300) and a BAND matrix (depth = n).
 
@@ -19,7 +19,11 @@ from __graft_entry__ import _load
 
 # name -> (prec, jacobi_steps)
 PRECS = {"identity": ("identity", 1), "jacobi": ("jacobi", 1), "neumann:2": ("neumann", 2), "neumann:4": ("neumann", 4),
-         "ilu": ("ilu", 1), "ilu_jacobi": ("ilu_jacobi", 5)}
+         "ilu": ("ilu", 1), "ilu_jacobi": ("ilu_jacobi", 5),
+         # on request (--precs): the Chebyshev polynomial, its interval from MPG_CHEB_RATIO / MPG_CHEB_LMAX
+         "chebyshev:2": ("chebyshev", 2), "chebyshev:3": ("chebyshev", 3), "chebyshev:4": ("chebyshev", 4),
+         "chebyshev:6": ("chebyshev", 6)}
+DEFAULT_PRECS = "identity,jacobi,neumann:2,neumann:4,ilu,ilu_jacobi"
 
 
 def main():
@@ -29,7 +33,7 @@ def main():
     ap.add_argument("--tol", type=float, default=0.0, help="also solve to this tolerance (0: fixed work only)")
     ap.add_argument("--max-restarts", type=int, default=2000)
     ap.add_argument("--accum", default="f64", choices=["f64", "f32"])
-    ap.add_argument("--precs", default=",".join(PRECS))
+    ap.add_argument("--precs", default=DEFAULT_PRECS)
     ap.add_argument("--matrices", default="LAP-1M,BAND-100k")
     args = ap.parse_args()
     mpg = _load()
@@ -53,9 +57,12 @@ def main():
             eng.sync()
             dt = time.perf_counter() - t
             its = eng.total_iters - it0
+            interval = eng.spmv_layout().get("prec_interval")
             eng.close()
             rec = {"matrix": name, "prec": pname, "rlen": args.rlen, "it_s": round(its / dt, 1),
                    "setup_s": round(setup, 3)}
+            if interval:
+                rec["prec_interval"] = [round(v, 6) for v in interval]
             if args.tol > 0:
                 r = mpg.solve(A, b, xt, engine="fused", tol=args.tol, max_restarts=args.max_restarts, **opts)
                 rec.update({"tol": args.tol, "status": r.status, "total_iters": int(r.total_iters),
