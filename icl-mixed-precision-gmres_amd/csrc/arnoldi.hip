@@ -9,10 +9,10 @@
 // then k_reduce_partials in a fixed order), which is also the seam where a
 // multi-GPU caller all-reduces across ranks.
 //
-// The kernels live in arnoldi_kernels.hpp, the launch code (templated on the
-// accumulation class) in arnoldi_launch.hpp; this file is the C-ABI and the
-// fp64-accumulation build, arnoldi_acc32.hip the fp32-accumulation one.
-#include "arnoldi_kernels.hpp"
+// The kernels live in one header per phase (arnoldi_plan.hpp lists them), the
+// launch code (templated on the accumulation class) in arnoldi_launch.hpp;
+// this file is the C-ABI and the fp64-accumulation build, arnoldi_acc32.hip
+// the fp32-accumulation one.
 #include "arnoldi_launch.hpp"
 
 #include <cstdlib>
@@ -104,22 +104,10 @@ int arnoldi_sell_build(mpg_arnoldi* a, int format) {
 
 
 // fp64 accumulation here; fp32 accumulation (mpg_arnoldi_set_accum, fp32
-// Arnoldi only) in arnoldi_acc32.hip
-int spmv_impl(mpg_arnoldi_t a, int k, int fold, bool dots = false) {
-    return a && a->acc32 ? mpg_acc32::spmv(a, k, fold, dots) : spmv_run<double>(a, k, fold, dots);
-}
-int dots_impl(mpg_arnoldi_t a, int k, bool combine) {
-    return a && a->acc32 ? mpg_acc32::dots(a, k, combine) : dots_run<double>(a, k, combine);
-}
-int cgs_impl(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials = false, bool no_next = false) {
-    return a && a->acc32 ? mpg_acc32::cgs(a, k, pass, givens, from_partials, no_next)
-                         : cgs_run<double>(a, k, pass, givens, from_partials, no_next);
-}
-int mgs_impl(mpg_arnoldi_t a, int k, int j, bool from_partials) {
-    return a && a->acc32 ? mpg_acc32::mgs(a, k, j, from_partials) : mgs_run<double>(a, k, j, from_partials);
-}
-int givens_impl(mpg_arnoldi_t a, int k, bool from_partials) {
-    return a && a->acc32 ? mpg_acc32::givens(a, k, from_partials) : givens_run<double>(a, k, from_partials);
+// Arnoldi only) in arnoldi_acc32.hip (a null workspace: this table's MPG_ERR_ARG)
+const mpg_arnoldi_phases& phases(const mpg_arnoldi* a) {
+    static const mpg_arnoldi_phases acc64 = phases_of<double>();
+    return a && a->acc32 ? mpg_arnoldi_phases_acc32() : acc64;
 }
 
 }  // namespace
@@ -284,19 +272,18 @@ int mpg_arnoldi_prologue(mpg_arnoldi_t a) {
             return sell_dispatch(*S, [&](auto ci, auto wc) {
                 using CI = decltype(ci);
                 return sell_dispatch_win(S->win, [&](auto wn) {
-                    auto go = [&](auto kern) {
-                        kern<<<grid, kBlock, 0, a->ctx->stream>>>(
-                            a->d.n, -a->front, a->d.n_ext, S->nslices, S->off, static_cast<const CI*>(S->col),
-                            static_cast<const X*>(S->val), static_cast<const X*>(a->d.x),
-                            static_cast<const X*>(a->d.b), diag, static_cast<T*>(a->w[0]), a->partial, S->sbase,
-                            S->spat, S->coff, static_cast<const CI*>(S->pat), S->xrp, S->xcol, static_cast<const X*>(S->xval),
-                            S->ustride, sell_xcd_order(*S) ? 1 : 0, S->rows);
+                    return with_flag(sell_uniform(*S), [&](auto uni) {
+                        std::apply(
+                            [&](auto... args) {
+                                k_prologue_sell<T, X, P, CI, decltype(wc)::value, decltype(wn)::value, decltype(uni)::value>
+                                    <<<grid, kBlock, 0, a->ctx->stream>>>(args...);
+                            },
+                            sell_args<CI, X>(a, *S,
+                                             std::make_tuple(static_cast<const X*>(a->d.x), static_cast<const X*>(a->d.b),
+                                                             diag, static_cast<T*>(a->w[0]), a->partial),
+                                             std::make_tuple(S->ustride, sell_xcd_order(*S) ? 1 : 0, S->rows)));
                         return (int)MPG_OK;
-                    };
-                    constexpr int Wc = decltype(wc)::value;
-                    constexpr bool WN = decltype(wn)::value;
-                    return sell_uniform(*S) ? go(k_prologue_sell<T, X, P, CI, Wc, WN, true>)
-                                            : go(k_prologue_sell<T, X, P, CI, Wc, WN, false>);
+                    });
                 });
             });
         }
@@ -371,29 +358,19 @@ int mpg_arnoldi_prologue_finish_partials(mpg_arnoldi_t a) {
     return MPG_OK;
 }
 
-int mpg_arnoldi_reduce(mpg_arnoldi_t a, int ncols) {
-    return a && a->acc32 ? mpg_acc32::reduce(a, ncols) : reduce_run<double>(a, ncols);
-}
+int mpg_arnoldi_reduce(mpg_arnoldi_t a, int ncols) { return phases(a).reduce(a, ncols); }
 
-int mpg_arnoldi_spmv(mpg_arnoldi_t a, int k) { return spmv_impl(a, k, 0); }
+int mpg_arnoldi_spmv(mpg_arnoldi_t a, int k) { return phases(a).spmv(a, k, 0, false); }
 int mpg_arnoldi_spmv_dots(mpg_arnoldi_t a, int k, int fold) {
     if (fold < 0 || fold > 2) return MPG_ERR_ARG;
-    return spmv_impl(a, k, fold, true);
+    return phases(a).spmv(a, k, fold, true);
 }
-int mpg_arnoldi_spmv_dots_supported(mpg_arnoldi_t a, int k) {
-    return a && a->acc32 ? mpg_acc32::spmv_dots_ok(a, k) : spmv_dots_check<double>(a, k);
-}
-int mpg_arnoldi_step_dots(mpg_arnoldi_t a, int k, int fold) {
-    return a && a->acc32 ? mpg_acc32::step_dots(a, k, fold) : step_dots_run<double>(a, k, fold);
-}
-int mpg_arnoldi_step_dots_supported(mpg_arnoldi_t a, int k) {
-    return a && a->acc32 ? mpg_acc32::step_dots_ok(a, k) : step_dots_check<double>(a, k);
-}
-int mpg_arnoldi_cgs_stream_at(mpg_arnoldi_t a, int k) {
-    return a && a->acc32 ? mpg_acc32::cgs_stream_at(a, k) : cgs_stream_check<double>(a, k);
-}
-int mpg_arnoldi_givens_spmv(mpg_arnoldi_t a, int k) { return spmv_impl(a, k, 1); }
-int mpg_arnoldi_givens_partials_spmv(mpg_arnoldi_t a, int k) { return spmv_impl(a, k, 2); }
+int mpg_arnoldi_spmv_dots_supported(mpg_arnoldi_t a, int k) { return phases(a).spmv_dots_ok(a, k); }
+int mpg_arnoldi_step_dots(mpg_arnoldi_t a, int k, int fold) { return phases(a).step_dots(a, k, fold); }
+int mpg_arnoldi_step_dots_supported(mpg_arnoldi_t a, int k) { return phases(a).step_dots_ok(a, k); }
+int mpg_arnoldi_cgs_stream_at(mpg_arnoldi_t a, int k) { return phases(a).cgs_stream_at(a, k); }
+int mpg_arnoldi_givens_spmv(mpg_arnoldi_t a, int k) { return phases(a).spmv(a, k, 1, false); }
+int mpg_arnoldi_givens_partials_spmv(mpg_arnoldi_t a, int k) { return phases(a).spmv(a, k, 2, false); }
 int mpg_arnoldi_fold_max_m(void) { return kFoldMaxM; }
 int mpg_arnoldi_partials_max_cols(void) { return kWideMax; }
 
@@ -420,26 +397,23 @@ int mpg_arnoldi_fold_pays(mpg_arnoldi_t a) {
     return (S.nslices + per_group - 1) / per_group <= limit ? 1 : 0;
 }
 
-int mpg_arnoldi_dots(mpg_arnoldi_t a, int k) { return dots_impl(a, k, false); }
-int mpg_arnoldi_dots_sums(mpg_arnoldi_t a, int k) { return dots_impl(a, k, true); }
+int mpg_arnoldi_dots(mpg_arnoldi_t a, int k) { return phases(a).dots(a, k, false); }
+int mpg_arnoldi_dots_sums(mpg_arnoldi_t a, int k) { return phases(a).dots(a, k, true); }
 
-int mpg_arnoldi_cgs(mpg_arnoldi_t a, int k, int pass) { return cgs_impl(a, k, pass, false); }
-int mpg_arnoldi_cgs_partials(mpg_arnoldi_t a, int k) { return cgs_impl(a, k, 0, false, true); }
-int mpg_arnoldi_cgs_givens(mpg_arnoldi_t a, int k, int pass) { return cgs_impl(a, k, pass, true); }
-int mpg_arnoldi_cgsr_wide_pass(mpg_arnoldi_t a, int k, int pass) { return cgs_impl(a, k, pass, false, true, true); }
+// (k, pass, givens, from_partials, no_next)
+int mpg_arnoldi_cgs(mpg_arnoldi_t a, int k, int pass) { return phases(a).cgs(a, k, pass, false, false, false); }
+int mpg_arnoldi_cgs_partials(mpg_arnoldi_t a, int k) { return phases(a).cgs(a, k, 0, false, true, false); }
+int mpg_arnoldi_cgs_givens(mpg_arnoldi_t a, int k, int pass) { return phases(a).cgs(a, k, pass, true, false, false); }
+int mpg_arnoldi_cgsr_wide_pass(mpg_arnoldi_t a, int k, int pass) { return phases(a).cgs(a, k, pass, false, true, true); }
 
-int mpg_arnoldi_mgs(mpg_arnoldi_t a, int k, int j) { return mgs_impl(a, k, j, false); }
-int mpg_arnoldi_mgs_partials(mpg_arnoldi_t a, int k, int j) { return mgs_impl(a, k, j, true); }
+int mpg_arnoldi_mgs(mpg_arnoldi_t a, int k, int j) { return phases(a).mgs(a, k, j, false); }
+int mpg_arnoldi_mgs_partials(mpg_arnoldi_t a, int k, int j) { return phases(a).mgs(a, k, j, true); }
 
-int mpg_arnoldi_givens(mpg_arnoldi_t a, int k) { return givens_impl(a, k, false); }
-int mpg_arnoldi_givens_partials(mpg_arnoldi_t a, int k) { return givens_impl(a, k, true); }
+int mpg_arnoldi_givens(mpg_arnoldi_t a, int k) { return phases(a).givens(a, k, false); }
+int mpg_arnoldi_givens_partials(mpg_arnoldi_t a, int k) { return phases(a).givens(a, k, true); }
 
-int mpg_arnoldi_update(mpg_arnoldi_t a, int k) {
-    return a && a->acc32 ? mpg_acc32::update(a, k) : update_run<double>(a, k);
-}
-int mpg_arnoldi_update_tail(mpg_arnoldi_t a, int m, int flags) {
-    return a && a->acc32 ? mpg_acc32::update_tail(a, m, flags) : update_tail_run<double>(a, m, flags);
-}
+int mpg_arnoldi_update(mpg_arnoldi_t a, int k) { return phases(a).update(a, k); }
+int mpg_arnoldi_update_tail(mpg_arnoldi_t a, int m, int flags) { return phases(a).update_tail(a, m, flags); }
 int mpg_arnoldi_update_tail_supported(mpg_arnoldi_t a) {
     return !a ? MPG_ERR_ARG : update_tail_ok(a) ? MPG_OK : MPG_ERR_UNSUPPORTED;
 }

@@ -1,14 +1,19 @@
 // Launch code of the fused Arnoldi phases, templated on the accumulation
-// class A of the fp32-Arnoldi kernels (arnoldi_kernels.hpp): arnoldi.hip
-// instantiates A = double for every type combination, arnoldi_acc32.hip A =
-// float for the fp32-Arnoldi combinations only (mpg_arnoldi_set_accum), each
-// in its own translation unit so the two builds compile in parallel.
+// class A of the fp32-Arnoldi kernels (arnoldi_spmv.hpp, arnoldi_dots.hpp,
+// arnoldi_orth.hpp, arnoldi_update.hpp): arnoldi.hip instantiates A = double
+// for every type combination, arnoldi_acc32.hip A = float for the
+// fp32-Arnoldi combinations only (mpg_arnoldi_set_accum), each in its own
+// translation unit so the two builds compile in parallel. Each hands its
+// launches out as one table (mpg_arnoldi_phases, phases_of<A>).
 #pragma once
 
-#include "arnoldi_kernels.hpp"
+#include "arnoldi_dots.hpp"
+#include "arnoldi_orth.hpp"
+#include "arnoldi_update.hpp"
 
 #include <algorithm>
 #include <cstdlib>
+#include <tuple>
 #include <type_traits>
 
 namespace {
@@ -40,7 +45,6 @@ int reduce_run(mpg_arnoldi_t a, int ncols) {
     return MPG_OK;
 }
 
-
 // fold: 0 plain; 1 Givens(k-1) folded, ||w||^2 from sums[0]; 2 from the partials.
 // dots: the panel dots fused (SellDots; MPG_ERR_UNSUPPORTED where the SELL
 // copy, an fp32 basis with fp32 values, int16 columns and the window are
@@ -51,6 +55,26 @@ int reduce_run(mpg_arnoldi_t a, int ncols) {
 #endif
 constexpr int kStepSellBlock = MPG_STEP_SELL_BLOCK;
 using kBlockC = std::integral_constant<int, kBlock>;
+
+// The argument list of a SELL kernel (the step's and the prologue's): the
+// slices of S with values of type V, the kernel's own operands `mid` behind
+// them, the slices' patterns and CSR-summed rows, and the kernel's `tail`.
+template <class CI, class V, class... M, class... E>
+auto sell_args(const mpg_arnoldi* a, const SellCopy& S, std::tuple<M...> mid, std::tuple<E...> tail) {
+    return std::tuple_cat(std::make_tuple(a->d.n, -a->front, a->d.n_ext, S.nslices, S.off, static_cast<const CI*>(S.col),
+                                          static_cast<const V*>(S.val)),
+                          mid,
+                          std::make_tuple(S.sbase, S.spat, S.coff, static_cast<const CI*>(S.pat), S.xrp, S.xcol,
+                                          static_cast<const V*>(S.xval)),
+                          tail);
+}
+
+// launch_timed of an argument tuple
+template <class K, class... X>
+int launch_tuple(mpg_ctx* c, K kern, dim3 grid, dim3 block, const std::tuple<X...>& args) {
+    std::apply([&](auto... x) { launch_timed(c, kern, grid, block, x...); }, args);
+    return MPG_OK;
+}
 
 // the status spmv_run(a, k, fold, dots = true) returns ahead of its launch
 template <class A>
@@ -83,18 +107,18 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
             return sell_dispatch(S, [&](auto ci, auto wc) {
                 using CI = decltype(ci);
                 constexpr int Wc = decltype(wc)::value;
+                // the step kernels' arguments (k_step_sell takes a sorted copy's rows behind them)
+                auto args = [&](SellDots dd) {
+                    return sell_args<CI, typename SellStore<VI>::type>(
+                        a, S,
+                        std::make_tuple(static_cast<const T*>(a->w[k & 1]), static_cast<const T*>(a->inv()),
+                                        static_cast<T*>(a->V), a->ld, k, diag, static_cast<T*>(a->w[(k + 1) & 1]), gf, dd),
+                        std::make_tuple(a->d.inner_row_exp, S.ustride, sell_xcd_order(S) ? 1 : 0));
+                };
                 auto launch = [&](auto kern, SellDots dd, auto bs) {
                     constexpr int BS = decltype(bs)::value;
                     const int grid = (S.nslices + BS / kWave - 1) / (BS / kWave);
-                    launch_timed(a->ctx, kern, dim3(grid), dim3(BS),
-                            a->d.n, -a->front, a->d.n_ext, S.nslices, S.off, static_cast<const CI*>(S.col),
-                            static_cast<const typename SellStore<VI>::type*>(S.val),
-                            static_cast<const T*>(a->w[k & 1]), static_cast<const T*>(a->inv()),
-                            static_cast<T*>(a->V), a->ld, k, diag, static_cast<T*>(a->w[(k + 1) & 1]), gf, dd,
-                            S.sbase, S.spat, S.coff, static_cast<const CI*>(S.pat), S.xrp, S.xcol,
-                            static_cast<const typename SellStore<VI>::type*>(S.xval), a->d.inner_row_exp,
-                            S.ustride, sell_xcd_order(S) ? 1 : 0, S.rows);
-                    return (int)MPG_OK;
+                    return launch_tuple(a->ctx, kern, dim3(grid), dim3(BS), std::tuple_cat(args(dd), std::make_tuple(S.rows)));
                 };
                 if constexpr (std::is_same_v<T, float> && std::is_same_v<VI, float> &&
                               std::is_same_v<CI, int16_t> && std::is_same_v<A, double>) {
@@ -102,8 +126,10 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
                         const SellDots dd{k + 1, a->fd_gs, a->fd_ng, a->fd_part, a->fd_cnt, a->dpart};
                         auto pick = [&](auto dn) {
                             constexpr int DN = decltype(dn)::value;
-                            return fold ? launch(k_step_sell<T, P, VI, CI, Wc, true, true, DN, kBlock, false, false, A>, dd, kBlockC())
-                                        : launch(k_step_sell<T, P, VI, CI, Wc, true, false, DN, kBlock, false, false, A>, dd, kBlockC());
+                            return with_flag(fold, [&](auto fo) {
+                                return launch(k_step_sell<T, P, VI, CI, Wc, true, decltype(fo)::value, DN, kBlock, false, false, A>,
+                                              dd, kBlockC());
+                            });
                         };
                         if (k + 1 <= 8) return pick(std::integral_constant<int, 8>());
                         if (k + 1 <= 16) return pick(std::integral_constant<int, 16>());
@@ -115,95 +141,69 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
                     using BSC = std::integral_constant<int, kStepSellBlock>;
                     const int be = sell_uniform(S) ? sell_pair(S) : 0;
                     if constexpr (std::is_same_v<CI, int16_t> && (Wc == 2 || Wc == 4)) if (be) {
-                        auto launch2 = [&](auto kern) {
-                            const int grid = (S.nslices + 2 * (kStepSellBlock / kWave) - 1) / (2 * (kStepSellBlock / kWave));
-                            launch_timed(a->ctx, kern, dim3(grid), dim3(kStepSellBlock),
-                                    a->d.n, -a->front, a->d.n_ext, S.nslices, S.off, static_cast<const CI*>(S.col),
-                                    static_cast<const typename SellStore<VI>::type*>(S.val),
-                                    static_cast<const T*>(a->w[k & 1]), static_cast<const T*>(a->inv()),
-                                    static_cast<T*>(a->V), a->ld, k, diag, static_cast<T*>(a->w[(k + 1) & 1]), gf,
-                                    SellDots{}, S.sbase, S.spat, S.coff, static_cast<const CI*>(S.pat), S.xrp, S.xcol,
-                                    static_cast<const typename SellStore<VI>::type*>(S.xval), a->d.inner_row_exp,
-                                    S.ustride, sell_xcd_order(S) ? 1 : 0);
-                            return (int)MPG_OK;
+                        // two slices per wave, at BE entries per row: 8 and 12, and 10 (Wc == 2, pregathered)
+                        auto pair = [&](auto bec, auto pgc) {
+                            return with_flag(fold, [&](auto fo) {
+                                const int grid = (S.nslices + 2 * (kStepSellBlock / kWave) - 1) / (2 * (kStepSellBlock / kWave));
+                                return launch_tuple(a->ctx,
+                                                    k_step_sell2<T, P, VI, Wc, WN, decltype(fo)::value, decltype(bec)::value,
+                                                                 kStepSellBlock, decltype(pgc)::value, A>,
+                                                    dim3(grid), dim3(kStepSellBlock), args(SellDots{}));
+                            });
                         };
                         const char* pge = std::getenv("MPG_SELL_PREGATHER");
-                        if (!WN && pge && *pge == '0') {
-                            if (be == 8)
-                                return fold ? launch2(k_step_sell2<T, P, VI, Wc, WN, true, 8, kStepSellBlock, false, A>)
-                                            : launch2(k_step_sell2<T, P, VI, Wc, WN, false, 8, kStepSellBlock, false, A>);
-                            return fold ? launch2(k_step_sell2<T, P, VI, Wc, WN, true, 12, kStepSellBlock, false, A>)
-                                        : launch2(k_step_sell2<T, P, VI, Wc, WN, false, 12, kStepSellBlock, false, A>);
-                        }
-                        if (be == 8)
-                            return fold ? launch2(k_step_sell2<T, P, VI, Wc, WN, true, 8, kStepSellBlock, true, A>)
-                                        : launch2(k_step_sell2<T, P, VI, Wc, WN, false, 8, kStepSellBlock, true, A>);
-                        if constexpr (Wc == 2) if (be == 10)
-                            return fold ? launch2(k_step_sell2<T, P, VI, Wc, WN, true, 10, kStepSellBlock, true, A>)
-                                        : launch2(k_step_sell2<T, P, VI, Wc, WN, false, 10, kStepSellBlock, true, A>);
-                        if (be != 12) return (int)MPG_ERR_UNSUPPORTED;
-                        return fold ? launch2(k_step_sell2<T, P, VI, Wc, WN, true, 12, kStepSellBlock, true, A>)
-                                    : launch2(k_step_sell2<T, P, VI, Wc, WN, false, 12, kStepSellBlock, true, A>);
+                        const bool pg = !(!WN && pge && *pge == '0');
+                        if constexpr (Wc == 2) if (pg && be == 10) return pair(std::integral_constant<int, 10>(), std::true_type());
+                        if (pg && be != 8 && be != 12) return (int)MPG_ERR_UNSUPPORTED;
+                        return with_flag(pg, [&](auto pgc) {
+                            return be == 8 ? pair(std::integral_constant<int, 8>(), pgc) : pair(std::integral_constant<int, 12>(), pgc);
+                        });
                     }
-                    if constexpr (!WN && !std::is_same_v<CI, int16_t>) if (sell_pipe(S)) {
-                        if (sell_uniform(S))
-                            return fold ? launch(k_step_sell<T, P, VI, CI, Wc, WN, true, 0, kStepSellBlock, true, true, A>,
-                                                 SellDots{}, BSC())
-                                        : launch(k_step_sell<T, P, VI, CI, Wc, WN, false, 0, kStepSellBlock, true, true, A>,
-                                                 SellDots{}, BSC());
-                        return fold ? launch(k_step_sell<T, P, VI, CI, Wc, WN, true, 0, kStepSellBlock, false, true, A>,
-                                             SellDots{}, BSC())
-                                    : launch(k_step_sell<T, P, VI, CI, Wc, WN, false, 0, kStepSellBlock, false, true, A>,
-                                             SellDots{}, BSC());
-                    }
-                    if (sell_uniform(S))
-                        return fold ? launch(k_step_sell<T, P, VI, CI, Wc, WN, true, 0, kStepSellBlock, true, false, A>,
-                                             SellDots{}, BSC())
-                                    : launch(k_step_sell<T, P, VI, CI, Wc, WN, false, 0, kStepSellBlock, true, false, A>,
-                                             SellDots{}, BSC());
-                    return fold ? launch(k_step_sell<T, P, VI, CI, Wc, WN, true, 0, kStepSellBlock, false, false, A>, SellDots{}, BSC())
-                                : launch(k_step_sell<T, P, VI, CI, Wc, WN, false, 0, kStepSellBlock, false, false, A>, SellDots{}, BSC());
+                    auto step = [&](auto pipe) {
+                        return with_flag(fold, [&](auto fo) {
+                            return with_flag(sell_uniform(S), [&](auto uni) {
+                                return launch(k_step_sell<T, P, VI, CI, Wc, WN, decltype(fo)::value, 0, kStepSellBlock,
+                                                          decltype(uni)::value, decltype(pipe)::value, A>,
+                                              SellDots{}, BSC());
+                            });
+                        });
+                    };
+                    if constexpr (!WN && !std::is_same_v<CI, int16_t>) if (sell_pipe(S)) return step(std::true_type());
+                    return step(std::false_type());
                 });
             });
         }
         if (a->node.nblk > 0) {
             const NodeCopy& S = a->node;
             const int tpw = node_tpw(S);
-            auto go = [&](auto kern) {
+            auto go = [&](auto kern, const P* dg) {
                 launch_timed(a->ctx, kern, dim3((S.ntiles + tpw - 1) / tpw), dim3(kBlock),
                              static_cast<const int32_t*>(S.tiles), static_cast<const int32_t*>(S.bptr),
                              static_cast<const char*>(S.recs), static_cast<const T*>(a->w[k & 1]),
-                             static_cast<const T*>(a->inv()), static_cast<T*>(a->V), a->ld, k, diag,
+                             static_cast<const T*>(a->inv()), static_cast<T*>(a->V), a->ld, k, dg,
                              static_cast<T*>(a->w[(k + 1) & 1]), gf, a->d.inner_row_exp, S.ntiles, S.nblk, tpw,
                              node_xcd(S));
                 return (int)MPG_OK;
             };
-            if (bj_fused(a)) {  // block Jacobi inside the launch (k_step_node_bj takes the inverses as `diag`)
-                auto gobj = [&](auto kern) {
-                    launch_timed(a->ctx, kern, dim3((S.ntiles + tpw - 1) / tpw), dim3(kBlock),
-                                 static_cast<const int32_t*>(S.tiles), static_cast<const int32_t*>(S.bptr),
-                                 static_cast<const char*>(S.recs), static_cast<const T*>(a->w[k & 1]),
-                                 static_cast<const T*>(a->inv()), static_cast<T*>(a->V), a->ld, k,
-                                 static_cast<const P*>(a->d.block_dinv), static_cast<T*>(a->w[(k + 1) & 1]), gf,
-                                 a->d.inner_row_exp, S.ntiles, S.nblk, tpw, node_xcd(S));
-                    return (int)MPG_OK;
-                };
-                return fold ? gobj(k_step_node_bj<T, P, VI, true, A>) : gobj(k_step_node_bj<T, P, VI, false, A>);
-            }
-            if (tpw > 1) return fold ? go(k_step_node<T, P, VI, true, true, A>) : go(k_step_node<T, P, VI, false, true, A>);
-            return fold ? go(k_step_node<T, P, VI, true, false, A>) : go(k_step_node<T, P, VI, false, false, A>);
+            return with_flag(fold, [&](auto fo) {
+                constexpr bool FOLD = decltype(fo)::value;
+                if (bj_fused(a))  // block Jacobi inside the launch (k_step_node_bj takes the inverses as `diag`)
+                    return go(k_step_node_bj<T, P, VI, FOLD, A>, static_cast<const P*>(a->d.block_dinv));
+                return with_flag(tpw > 1, [&](auto walk) {
+                    return go(k_step_node<T, P, VI, FOLD, decltype(walk)::value, A>, diag);
+                });
+            });
         }
-        const int mode = csr_mode();
-        auto kern = mode == 1   ? (fold ? k_step_spmv<T, P, VI, true, 1, A> : k_step_spmv<T, P, VI, false, 1, A>)
-                    : mode == 2 ? (fold ? k_step_spmv<T, P, VI, true, 2, A> : k_step_spmv<T, P, VI, false, 2, A>)
-                    : mode == 3 ? (fold ? k_step_spmv<T, P, VI, true, 3, A> : k_step_spmv<T, P, VI, false, 3, A>)
-                    : mode == 4 ? (fold ? k_step_spmv<T, P, VI, true, 4, A> : k_step_spmv<T, P, VI, false, 4, A>)
-                                : (fold ? k_step_spmv<T, P, VI, true, 0, A> : k_step_spmv<T, P, VI, false, 0, A>);
-        launch_timed(a->ctx, kern, dim3(rb_grid(a)), dim3(kBlock),
-            Acsr->blocks, Acsr->nblocks, Acsr->rowptr, Acsr->col, static_cast<const VI*>(a->d.val_inner), Acsr->nnz,
-            static_cast<const T*>(a->w[k & 1]), static_cast<const T*>(a->inv()), static_cast<T*>(a->V), a->ld, k,
-            diag, static_cast<T*>(a->w[(k + 1) & 1]), gf, a->d.inner_row_exp);
-        return (int)MPG_OK;
+        return with_int<4>(csr_mode(), [&](auto mode) {
+            return with_flag(fold, [&](auto fo) {
+                launch_timed(a->ctx, k_step_spmv<T, P, VI, decltype(fo)::value, decltype(mode)::value, A>, dim3(rb_grid(a)),
+                    dim3(kBlock), Acsr->blocks, Acsr->nblocks, Acsr->rowptr, Acsr->col,
+                    static_cast<const VI*>(a->d.val_inner), Acsr->nnz, static_cast<const T*>(a->w[k & 1]),
+                    static_cast<const T*>(a->inv()), static_cast<T*>(a->V), a->ld, k, diag,
+                    static_cast<T*>(a->w[(k + 1) & 1]), gf, a->d.inner_row_exp);
+                return (int)MPG_OK;
+            });
+        });
     });
     if (st) return st;
     if (dots) {
@@ -213,7 +213,6 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
 }
-
 
 // The SpMV of step k inside the panel dots' launch (k_step_dots): MPG_OK when
 // this workspace, accumulation class and step can run it, MPG_ERR_UNSUPPORTED
@@ -260,18 +259,18 @@ int step_dots_run(mpg_arnoldi_t a, int k, int fold) {
         const P* diag = a->d.jacobi ? static_cast<const P*>(a->d.diag) : nullptr;
         int st = with_nc<kNC>(k + 1, [&](auto nc) {
             constexpr int NC = decltype(nc)::value;
-            auto go = [&](auto kern) {
+            // (PF, the held first batch of basis columns: 27.54k against 27.05k it/s
+            // without it on BAND-10M, 3 interleaved runs each; only that form is built)
+            return with_flag(fold, [&](auto fo) {
                 // (with the fold one workgroup more, last in the grid: the rider that runs the Givens step)
-                launch_timed(a->ctx, kern, dim3(a->Gd + (fold ? 1 : 0)), dim3(kCombineBlock), a->d.n, S.nslices,
+                launch_timed(a->ctx, k_step_dots<T, P, 2, decltype(fo)::value, 10, NC, true, A>,
+                             dim3(a->Gd + (fold ? 1 : 0)), dim3(kCombineBlock), a->d.n, S.nslices,
                              static_cast<const int16_t*>(S.col), static_cast<const T*>(S.val),
                              static_cast<const T*>(a->w[k & 1]), static_cast<const T*>(a->inv()),
                              static_cast<T*>(a->V), a->ld, k, diag, static_cast<T*>(a->w[(k + 1) & 1]), gf, S.spat,
                              S.coff, static_cast<const int16_t*>(S.pat), S.ustride, a->dpart);
                 return (int)MPG_OK;
-            };
-            // (PF, the held first batch of basis columns: 27.54k against 27.05k it/s
-            // without it on BAND-10M, 3 interleaved runs each; only that form is built)
-            return fold ? go(k_step_dots<T, P, 2, true, 10, NC, true, A>) : go(k_step_dots<T, P, 2, false, 10, NC, true, A>);
+            });
         });
         if (st) return st;
         a->last_G = a->Gd;
@@ -317,16 +316,12 @@ int dots_run(mpg_arnoldi_t a, int k, bool combine) {
         }
         if (ndots_all <= kNC) {  // one panel: 1024-thread workgroups, one per CU -> Gd partials per column
             return with_nc<kNC>(ndots_all, [&](auto nc) {
-                constexpr int NC = decltype(nc)::value;
-                const T* Vp = static_cast<const T*>(a->V);
-                const T* wp = static_cast<const T*>(a->w[(k + 1) & 1]);
-                if (sp)
-                    k_dots_nc<T, kCombineBlock, NC, true, A>
-                        <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, Vp, a->ld, wp, a->dpart, sp);
-                else
-                    k_dots_nc<T, kCombineBlock, NC, false, A>
-                        <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, Vp, a->ld, wp, a->dpart, nullptr);
-                return (int)MPG_OK;
+                return with_flag(sp != nullptr, [&](auto stamped) {
+                    k_dots_nc<T, kCombineBlock, decltype(nc)::value, decltype(stamped)::value, A>
+                        <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, static_cast<const T*>(a->V), a->ld,
+                                                                       static_cast<const T*>(a->w[(k + 1) & 1]), a->dpart, sp);
+                    return (int)MPG_OK;
+                });
             });
         }
         if (ndots_all <= kWideMax) {  // every panel in one launch -> wide_groups(a, k) partials per column
@@ -354,7 +349,6 @@ int dots_run(mpg_arnoldi_t a, int k, bool combine) {
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
 }
-
 
 // The in-launch-sum CGS update issuing its first row group under the
 // coefficient sums (k_cgs_update_nc<..., PF>, steps with k + 1 <= one batch
@@ -452,12 +446,11 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
                 return (int)MPG_OK;
             });
         } else if (next_dots) {
-            if (from_partials)
-                k_cgs_update<T, true, false, kBlock, true, A><<<row_grid(a), kBlock, 0, a->ctx->stream>>>(
+            with_flag(from_partials, [&](auto fp) {  // (part_G: 0 unless from_partials)
+                k_cgs_update<T, true, false, kBlock, decltype(fp)::value, A><<<row_grid(a), kBlock, 0, a->ctx->stream>>>(
                     a->d.n, static_cast<const T*>(a->V), a->ld, k, src, coef_out, w, a->partial, nullptr, g, part_G);
-            else
-                k_cgs_update<T, true, false, kBlock, false, A><<<row_grid(a), kBlock, 0, a->ctx->stream>>>(
-                    a->d.n, static_cast<const T*>(a->V), a->ld, k, src, coef_out, w, a->partial, nullptr, g, 0);
+                return (int)MPG_OK;
+            });
             for (int c0 = kNC; c0 < k + 1; c0 += kNC) {
                 const int nc = k + 1 - c0 < kNC ? k + 1 - c0 : kNC;
                 k_panel_dots<T, kBlock, false, A><<<row_grid(a), kBlock, 0, a->ctx->stream>>>(
@@ -501,16 +494,15 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
                         return (int)MPG_OK;
                     }
                 }
-                if (from_partials && sp)
-                    k_cgs_update_nc<T, kCombineBlock, NC, true, false, false, true, A>
-                        <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, Vp, a->ld, src, part_G, coef_out, w,
-                                                                       a->partial, sp);
-                else if (from_partials)
-                    k_cgs_update_nc<T, kCombineBlock, NC, true, false, false, false, A><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
-                        a->d.n, Vp, a->ld, src, part_G, coef_out, w, a->partial, nullptr);
-                else
-                    k_cgs_update_nc<T, kCombineBlock, NC, false, false, false, false, A><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
-                        a->d.n, Vp, a->ld, src, 0, coef_out, w, a->partial, nullptr);
+                if (from_partials)  // (sp: only with from_partials, above)
+                    return with_flag(sp != nullptr, [&](auto stamped) {
+                        k_cgs_update_nc<T, kCombineBlock, NC, true, false, false, decltype(stamped)::value, A>
+                            <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, Vp, a->ld, src, part_G, coef_out, w,
+                                                                           a->partial, sp);
+                        return (int)MPG_OK;
+                    });
+                k_cgs_update_nc<T, kCombineBlock, NC, false, false, false, false, A><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
+                    a->d.n, Vp, a->ld, src, 0, coef_out, w, a->partial, nullptr);
                 return (int)MPG_OK;
             });
         } else {
@@ -525,7 +517,6 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
 }
-
 
 template <class A>
 int mgs_run(mpg_arnoldi_t a, int k, int j, bool from_partials) {
@@ -551,7 +542,6 @@ int mgs_run(mpg_arnoldi_t a, int k, int j, bool from_partials) {
     return MPG_OK;
 }
 
-
 template <class A>
 int givens_run(mpg_arnoldi_t a, int k, bool from_partials) {
     if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
@@ -565,7 +555,6 @@ int givens_run(mpg_arnoldi_t a, int k, bool from_partials) {
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
 }
-
 
 template <class A>
 int update_run(mpg_arnoldi_t a, int k) {
@@ -604,7 +593,6 @@ int update_run(mpg_arnoldi_t a, int k) {
     return MPG_OK;
 }
 
-
 // givens_partials(m - 1) + update(m) (+ the x snapshot, flags bit 0) in one
 // launch (k_update_tail_nc): the whole restart length in one panel, and the
 // ||w||^2 partials of a 1024-thread producer (at most kBlock of them, which
@@ -625,17 +613,14 @@ int update_tail_run(mpg_arnoldi_t a, int m, int flags) {
         const UpdateTail<T> tl{GivensFold<T>{a->last_part, a->last_G, givens_args<T>(a, m - 1)},
                                static_cast<T*>(a->tail_stage())};
         return with_nc<kNC>(m, [&](auto nc) {
-            constexpr int NC = decltype(nc)::value;
-            constexpr bool stream = std::is_same_v<T, float> && std::is_same_v<A, float>;
-            const T* Vp = static_cast<const T*>(a->V);
-            X* xp = static_cast<X*>(a->d.x);
-            if (flags & 1)
-                k_update_tail_nc<T, X, NC, A, stream, true><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
-                    a->d.n, Vp, a->ld, xp, static_cast<X*>(a->x_snap), tl);
-            else
-                k_update_tail_nc<T, X, NC, A, stream, false><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
-                    a->d.n, Vp, a->ld, xp, nullptr, tl);
-            return (int)MPG_OK;
+            return with_flag(flags & 1, [&](auto snap) {
+                constexpr bool stream = std::is_same_v<T, float> && std::is_same_v<A, float>;
+                constexpr bool SNAP = decltype(snap)::value;
+                k_update_tail_nc<T, X, decltype(nc)::value, A, stream, SNAP><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
+                    a->d.n, static_cast<const T*>(a->V), a->ld, static_cast<X*>(a->d.x),
+                    SNAP ? static_cast<X*>(a->x_snap) : nullptr, tl);
+                return (int)MPG_OK;
+            });
         });
     });
     if (st) return st;
@@ -644,22 +629,32 @@ int update_tail_run(mpg_arnoldi_t a, int m, int flags) {
     return MPG_OK;
 }
 
-
 }  // namespace
 
-// The A = float launches, compiled in arnoldi_acc32.hip (fp32 Arnoldi only:
-// an fp64 combination returns MPG_ERR_UNSUPPORTED there).
-namespace mpg_acc32 {
-int reduce(mpg_arnoldi* a, int ncols);
-int spmv(mpg_arnoldi* a, int k, int fold, bool dots);
-int step_dots(mpg_arnoldi* a, int k, int fold);
-int step_dots_ok(const mpg_arnoldi* a, int k);
-int cgs_stream_at(const mpg_arnoldi* a, int k);
-int spmv_dots_ok(const mpg_arnoldi* a, int k);
-int dots(mpg_arnoldi* a, int k, bool combine);
-int cgs(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool no_next);
-int mgs(mpg_arnoldi* a, int k, int j, bool from_partials);
-int givens(mpg_arnoldi* a, int k, bool from_partials);
-int update(mpg_arnoldi* a, int k);
-int update_tail(mpg_arnoldi* a, int m, int flags);
-}  // namespace mpg_acc32
+// The phase launches and queries of one accumulation class. arnoldi.hip
+// holds the A = double table, arnoldi_acc32.hip the A = float one (fp32
+// Arnoldi only: an fp64 combination returns MPG_ERR_UNSUPPORTED there).
+struct mpg_arnoldi_phases {
+    int (*reduce)(mpg_arnoldi* a, int ncols);
+    int (*spmv)(mpg_arnoldi* a, int k, int fold, bool dots);
+    int (*step_dots)(mpg_arnoldi* a, int k, int fold);
+    int (*step_dots_ok)(const mpg_arnoldi* a, int k);
+    int (*spmv_dots_ok)(const mpg_arnoldi* a, int k);
+    int (*cgs_stream_at)(const mpg_arnoldi* a, int k);
+    int (*dots)(mpg_arnoldi* a, int k, bool combine);
+    int (*cgs)(mpg_arnoldi* a, int k, int pass, bool givens, bool from_partials, bool no_next);
+    int (*mgs)(mpg_arnoldi* a, int k, int j, bool from_partials);
+    int (*givens)(mpg_arnoldi* a, int k, bool from_partials);
+    int (*update)(mpg_arnoldi* a, int k);
+    int (*update_tail)(mpg_arnoldi* a, int m, int flags);
+};
+// (a function, not an object: host code only, so the device compilation never sees the table)
+__attribute__((visibility("hidden"))) const mpg_arnoldi_phases& mpg_arnoldi_phases_acc32();
+
+namespace {
+template <class A>
+mpg_arnoldi_phases phases_of() {
+    return {reduce_run<A>, spmv_run<A>,     step_dots_run<A>, step_dots_check<A>, spmv_dots_check<A>, cgs_stream_check<A>,
+            dots_run<A>,   cgs_run<A>,      mgs_run<A>,       givens_run<A>,      update_run<A>,      update_tail_run<A>};
+}
+}  // namespace

@@ -250,7 +250,7 @@ __device__ __forceinline__ T block_max(T v, T* scratch) {
 
 template <class T> struct acc_type { using type = double; };
 
-// acc + a * b in the accumulation class of a kernel (arnoldi_kernels.hpp):
+// acc + a * b in the accumulation class of a kernel (arnoldi_plan.hpp):
 // fp64 (one fused multiply-add), or fp32 -- the fp64 product (exact for
 // fp32 / fp16 operands) rounded to fp32, then an fp32 add: the same two
 // roundings in every storage format (SELL, node blocks, CSR tiles), so the

@@ -29,7 +29,7 @@
 // mpg_cheb_coeffs. The fourth epilogue operand z_prev[i] is loaded with the
 // other three; z_out may alias it too. mpg_csr_jacobi_bound_* is the
 // Gershgorin bound of D A that gives b.
-#include "arnoldi_kernels.hpp"
+#include "arnoldi_prologue.hpp"
 #include "mpgmres/solve.h"
 
 #include <cmath>

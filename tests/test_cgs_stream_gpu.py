@@ -18,7 +18,7 @@ from tests.test_step_dots_gpu import _same
 
 pytestmark = pytest.mark.gpu
 
-RING = 9  # kStreamSlots (csrc/arnoldi_kernels.hpp)
+RING = 9  # kStreamSlots (csrc/lds_ring.hpp)
 _PROBLEMS = {}
 
 

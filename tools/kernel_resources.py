@@ -1,7 +1,9 @@
 """Register / LDS / scratch / occupancy of every gfx950 kernel in a HIP source,
 from hipcc's kernel-resource-usage remarks (no GPU needed).
 
-usage: python tools/kernel_resources.py csrc/arnoldi.hip [name-filter]
+usage: python tools/kernel_resources.py icl-mixed-precision-gmres_amd/csrc/arnoldi.hip [name-filter]
+(the kernels of the per-phase headers, csrc/arnoldi_*.hpp, through the .hip that instantiates
+them: arnoldi.hip the fp64 accumulation class, arnoldi_acc32.hip the fp32 one)
 """
 import re
 import subprocess
