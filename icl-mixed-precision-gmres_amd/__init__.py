@@ -216,6 +216,9 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_prec_sweeps.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_interval.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.mpg_cheb_coeffs.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.mpg_engine_prec_roots.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]
+    lib.mpg_gmres_poly_roots.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.mpg_engine_prologue_format.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.restype = C.c_int64
@@ -306,6 +309,13 @@ _HIP_DECLS.update({
     "mpg_csr_jacobi_bound_f64": ([_P, _P, _P, _P, C.POINTER(C.c_double)], C.c_int),
     "mpg_csr_jacobi_bound_f32": ([_P, _P, _P, _P, C.POINTER(C.c_double)], C.c_int),
     "mpg_arnoldi_cheb_apply": ([_P, _I32, C.c_double, C.c_double, _P, _P, _P], C.c_int),
+    "mpg_csr_poly_sweep_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_double, C.c_double], C.c_int),
+    "mpg_csr_poly_sweep_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, C.c_float], C.c_int),
+    "mpg_sell_poly_sweep_f64": ([_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_double, C.c_double], C.c_int),
+    "mpg_sell_poly_sweep_f32": ([_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, C.c_float], C.c_int),
+    "mpg_arnoldi_poly_apply": ([_P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P], C.c_int),
+    "mpg_gmres_poly_roots": ([C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_int)], C.c_int),
     "mpg_arnoldi_create": ([_P, _P, C.POINTER(_P)], C.c_int),
     "mpg_arnoldi_destroy": ([_P], C.c_int),
     "mpg_arnoldi_set_accum": ([_P, C.c_int], C.c_int),
@@ -964,7 +974,10 @@ class Engine:
         prec="neumann" and prec="chebyshev" it reports "prec_sweeps": the
         sweeps per application (mpg_engine_prec_sweeps); with prec="chebyshev"
         also "prec_interval": the interval (a, b) its coefficients were built
-        for (mpg_engine_prec_interval)."""
+        for (mpg_engine_prec_interval). With prec="gmres_poly" it reports
+        "prec_sweeps", the number of roots, and "prec_roots": the roots as a
+        list of complex numbers in the order they are applied
+        (mpg_engine_prec_roots)."""
         f, w, cb, st, win = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         if self._lib.mpg_engine_spmv_layout(self._h, C.byref(f), C.byref(w), C.byref(cb), C.byref(st), C.byref(win)):
             raise RuntimeError("mpg_engine_spmv_layout failed")
@@ -973,6 +986,8 @@ class Engine:
         ps = int(self._lib.mpg_engine_prec_sweeps(self._h))
         ia, ib = C.c_double(), C.c_double()
         has_iv = self._lib.mpg_engine_prec_interval(self._h, C.byref(ia), C.byref(ib)) == 0
+        rre, rim = (C.c_double * 64)(), (C.c_double * 64)()
+        nroots = int(self._lib.mpg_engine_prec_roots(self._h, rre, rim, 64))
         stream = int(self._lib.mpg_engine_cgs_stream_steps(self._h))
         rider = int(self._lib.mpg_engine_givens_rider(self._h)) == 1
         tail = int(self._lib.mpg_engine_tail_fold(self._h)) == 1
@@ -986,6 +1001,7 @@ class Engine:
                 **({"prec_fused": pf} if pf >= 0 else {}),
                 **({"prec_sweeps": ps} if ps >= 0 else {}),
                 **({"prec_interval": (ia.value, ib.value)} if has_iv else {}),
+                **({"prec_roots": [complex(rre[i], rim[i]) for i in range(nroots)]} if nroots >= 0 else {}),
                 "prologue": {1: "csr", 2: "sell", 3: "node"}[int(self._lib.mpg_engine_prologue_format(self._h))]}
 
     def step_dots_status(self, k: int) -> int:

@@ -6,7 +6,8 @@ import ctypes as C
 
 MODES = {"mixed": 0, "baseline": 1, "single-prec": 2, "single": 3, "mixed-half": 4}
 ORTHS = {"cgs": 0, "mgs": 1, "cgsr": 2}
-PRECS = {"ilu": 0, "ilu_jacobi": 1, "jacobi": 2, "identity": 3, "bjacobi": 4, "neumann": 5, "chebyshev": 6}
+PRECS = {"ilu": 0, "ilu_jacobi": 1, "jacobi": 2, "identity": 3, "bjacobi": 4, "neumann": 5, "chebyshev": 6,
+         "gmres_poly": 7}
 ENGINES = {"surface": 0, "fused": 1}
 SPMV_FORMATS = {"auto": 0, "csr": 1, "sell": 2, "node": 3}
 ACCUMS = {"f64": 0, "f32": 1}  # mpg_solve_args.accum (MPG_ACCUM_F64 / MPG_ACCUM_F32, arnoldi.h)

@@ -29,6 +29,17 @@
 // mpg_cheb_coeffs. The fourth epilogue operand z_prev[i] is loaded with the
 // other three; z_out may alias it too. mpg_csr_jacobi_bound_* is the
 // Gershgorin bound of D A that gives b.
+//
+// The GMRES polynomial (roots theta_i, residual polynomial prod (1 - x / theta_i))
+// is applied in product form through four more epilogues (kPoly*): with
+// B = D A, the running product p and the result z, a real root's step is
+// p <- p - (1 / theta) B p, z <- z + (1 / theta_next) p; a pair a +- b i takes
+// t = 2 a p - B p, z <- z + c t and then p <- p - c B t, c = 1 / (a^2 + b^2)
+// (poly_update below; capi.h states each operation). There z is read and
+// written by row i's lane alone, so it is one vector; the gathered vector may
+// differ from the lane's own operand p (a pair's second half gathers t), and
+// the second output may be p, never the gathered vector. mpg_gmres_poly_roots
+// gives the roots in the order the product is stable in.
 #include "arnoldi_prologue.hpp"
 #include "mpgmres/solve.h"
 
@@ -41,8 +52,20 @@ using namespace mpg;
 namespace {
 
 // The sweep's epilogue: the Neumann step, the Chebyshev step, and the first
-// Chebyshev step (z_prev = 0: no fourth operand)
-enum : int { kNeumann = 0, kCheb = 1, kChebFirst = 2 };
+// Chebyshev step (z_prev = 0: no fourth operand); the GMRES polynomial's step
+// and pair (the first half of a pair), each also in the form that reads no z
+enum : int {
+    kNeumann = 0,
+    kCheb = 1,
+    kChebFirst = 2,
+    kPolyStep = 4,
+    kPolyStepFirst = 5,
+    kPolyPair = 6,
+    kPolyPairFirst = 7
+};
+constexpr bool poly_form(int e) { return e >= kPolyStep; }
+constexpr bool poly_pair(int e) { return e == kPolyPair || e == kPolyPairFirst; }
+constexpr bool poly_first(int e) { return e == kPolyStepFirst || e == kPolyPairFirst; }
 
 // what the Chebyshev epilogues take besides the Neumann operands (z_prev
 // carries no __restrict__: z_out may be that vector)
@@ -65,6 +88,8 @@ struct SweepOps<T, kCheb> {
 template <int E, class T>
 __device__ __forceinline__ SweepOps<T, E> sweep_ops(const T* r, const T* dinv, const T* z_in, const T* z_prev, int i) {
     if constexpr (E == kCheb) return {r[i], dinv[i], z_in[i], z_prev[i]};
+    else if constexpr (poly_first(E)) return {r[i], dinv[i], T(0)};  // (the first form reads no z)
+    else if constexpr (poly_form(E)) return {r[i], dinv[i], z_prev[i]};  // p (passed as r), d, z (passed as z_prev)
     else return {r[i], dinv[i], z_in[i]};
 }
 
@@ -88,6 +113,45 @@ __device__ __forceinline__ T sweep_update(T s, const SweepOps<T, E>& o, T alpha,
     }
 }
 
+// The GMRES polynomial's forms, o.r the lane's own operand p and o.z its z
+// (the first forms: z = w0 p, w0 = c0 for a step, 0 for a pair). Step, c0 =
+// omega, c1 = omega_next: u = d s; v = c0 u; o = p - v; y = c1 o. Pair's first
+// half, c0 = 2 a, c1 = 1 / (a^2 + b^2): u = d s; q = c0 p; t = q - u; y = c1 t.
+// Then z + y and the second output (o or t). Each rounded to T.
+template <int E, class T>
+__device__ __forceinline__ void poly_update(T s, const SweepOps<T, E>& o, T c0, T c1, T& z, T& out) {
+#pragma clang fp contract(off)
+    const T u = o.d * s;
+    T zin = o.z;
+    if constexpr (poly_first(E)) zin = (poly_pair(E) ? T(0) : c0) * o.r;
+    T y;
+    if constexpr (poly_pair(E)) {
+        const T q = c0 * o.r;
+        out = q - u;
+        y = c1 * out;
+    } else {
+        const T v = c0 * u;
+        out = o.r - v;
+        y = c1 * out;
+    }
+    z = zin + y;
+}
+
+// row i's stores: z_out of the Neumann and Chebyshev steps; z (in place) and,
+// unless it is the last form (no z_out), the second output of the GMRES
+// polynomial's
+template <int E, class T>
+__device__ __forceinline__ void sweep_store(int i, T s, const SweepOps<T, E>& o, T* z_out, const ChebArgs<T>& ch) {
+    if constexpr (poly_form(E)) {
+        T z, out;
+        poly_update<E>(s, o, ch.alpha, ch.beta, z, out);
+        const_cast<T*>(ch.z_prev)[i] = z;
+        if (z_out) z_out[i] = out;
+    } else {
+        z_out[i] = sweep_update<E>(s, o, ch.alpha, ch.beta);
+    }
+}
+
 // (r and z_out carry no __restrict__: they may be one vector)
 template <class T, class A, int E>
 __global__ __launch_bounds__(kBlock) void k_csr_sweep(const int32_t* __restrict__ blocks, int nblocks,
@@ -100,8 +164,7 @@ __global__ __launch_bounds__(kBlock) void k_csr_sweep(const int32_t* __restrict_
     for_rows<false, false, A>(
         blocks, nblocks, rowptr, col, val, nnz, [&](int c) { return (double)z_in[c]; },
         [&](int i) { return sweep_ops<E>(r, dinv, z_in, ch.z_prev, i); },
-        [&](int i, A sum, const SweepOps<T, E>& o) { z_out[i] = sweep_update<E>((T)sum, o, ch.alpha, ch.beta); }, prod,
-        scratch);
+        [&](int i, A sum, const SweepOps<T, E>& o) { sweep_store<E>(i, (T)sum, o, z_out, ch); }, prod, scratch);
 }
 
 template <class T, class CI, int W, bool UNI, class A, int E>
@@ -142,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const
             row.sum(q, xv, sum);
         }
     }
-    if (i < n) z_out[i] = sweep_update<E>((T)sum, o, ch.alpha, ch.beta);
+    if (i < n) sweep_store<E>(i, (T)sum, o, z_out, ch);
 }
 
 template <class T, class A, int E>
@@ -224,6 +287,50 @@ int sell_cheb_api(mpg_ctx* ctx, mpg_sell* M, const T* dinv, const T* r, const T*
                                  alpha, beta);
 }
 
+// one sweep of the GMRES polynomial on either storage: g gathered, p the
+// lane's own operand, z in place, out the second output (NULL: the last form)
+template <class T, class A>
+int poly_sweep(mpg_ctx* ctx, const SellCopy* S, const mpg_csr* M, int grid, const T* vals, const T* dinv, const T* g,
+               const T* p, T* z, T* out, bool pair, bool first, T c0, T c1) {
+    const ChebArgs<T> ch{z, c0, c1};
+    auto go = [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        return S ? sell_sweep<T, A, E>(ctx, *S, dinv, p, g, out, ch)
+                 : csr_sweep<T, A, E>(ctx, M, grid, vals, dinv, p, g, out, ch);
+    };
+    if (pair)
+        return first ? go(std::integral_constant<int, kPolyPairFirst>{}) : go(std::integral_constant<int, kPolyPair>{});
+    return first ? go(std::integral_constant<int, kPolyStepFirst>{}) : go(std::integral_constant<int, kPolyStep>{});
+}
+
+// the vectors of one sweep: out is absent exactly in the last form and is
+// never the gathered vector; z is nobody else's
+template <class T>
+bool poly_vectors_ok(const T* dinv, const T* g, const T* p, const T* z, const T* out, int form, int last) {
+    if (!dinv || !g || !p || !z || (form != MPG_POLY_STEP && form != MPG_POLY_PAIR)) return false;
+    if (last ? out != nullptr : out == nullptr) return false;
+    return out != g && z != g && z != p && z != out;
+}
+
+template <class T>
+int csr_poly_api(mpg_ctx* ctx, mpg_csr* M, const T* vals, const T* dinv, const T* g, const T* p, T* z, T* out, int form,
+                 int first, int last, T c0, T c1) {
+    if (!ctx || !M || M->rows != M->cols || (M->nnz > 0 && !vals)) return MPG_ERR_ARG;
+    if (M->rows > 0 && !poly_vectors_ok(dinv, g, p, z, out, form, last)) return MPG_ERR_ARG;
+    if (M->rows == 0) return MPG_OK;
+    return poly_sweep<T, double>(ctx, nullptr, M, M->nblocks, vals, dinv, g, p, z, out, form == MPG_POLY_PAIR,
+                                 first != 0, c0, c1);
+}
+
+template <class T, int VT>
+int sell_poly_api(mpg_ctx* ctx, mpg_sell* M, const T* dinv, const T* g, const T* p, T* z, T* out, int form, int first,
+                  int last, T c0, T c1) {
+    if (!ctx || !M || M->S.vtype != VT || M->cols != M->S.n) return MPG_ERR_ARG;
+    if (M->S.n > 0 && !poly_vectors_ok(dinv, g, p, z, out, form, last)) return MPG_ERR_ARG;
+    return poly_sweep<T, double>(ctx, &M->S, nullptr, 0, static_cast<const T*>(nullptr), dinv, g, p, z, out,
+                                 form == MPG_POLY_PAIR, first != 0, c0, c1);
+}
+
 template <class T>
 int gdmv_t(mpg_ctx* ctx, int64_t n, T alpha, const T* d, const T* x, T* y) {
     if constexpr (std::is_same_v<T, double>) return mpg_gdmv_f64(ctx, n, alpha, d, x, 0.0, y);
@@ -274,6 +381,201 @@ int cheb_run(mpg_arnoldi* a, int steps, double theta, double delta, T* w, T* wor
             return st;
     }
     return MPG_OK;
+}
+
+// a root list mpg_arnoldi_poly_apply takes: finite, nonzero, every member with
+// im > 0 followed by its conjugate (the same bits of re, the opposite im)
+bool poly_roots_ok(int count, const double* re, const double* im) {
+    if (count < 1 || count > 64 || !re || !im) return false;
+    for (int k = 0; k < count; ++k) {
+        if (!std::isfinite(re[k]) || !std::isfinite(im[k]) || (re[k] == 0.0 && im[k] == 0.0)) return false;
+        if (im[k] < 0.0) return false;  // (a conjugate is consumed with its partner below)
+        if (im[k] > 0.0) {
+            if (k + 1 >= count || re[k + 1] != re[k] || im[k + 1] != -im[k]) return false;
+            ++k;
+        }
+    }
+    return true;
+}
+
+// The product form on the workspace's storage. p_0 = D w into work0, z in w
+// from the first sweep on; a real root's step gathers p from `cur` and stores
+// the new p into the other work vector; a pair's first half stores t there and
+// its second half gathers t and stores the new p over `cur`. The coefficients
+// are formed in fp64 and rounded once to T. A final real root's term came with
+// the sweep before it (omega_next); a final pair runs its first half alone.
+template <class T, class A>
+int poly_run(mpg_arnoldi* a, int count, const double* re, const double* im, T* w, T* work0, T* work1) {
+#pragma clang fp contract(off)
+    mpg_ctx* ctx = a->ctx;
+    const T* d = static_cast<const T*>(a->d.diag);
+    const int n = a->d.n;
+    if (count == 1) return gdmv_t<T>(ctx, n, (T)(1.0 / re[0]), d, w, w);
+    if (int st = gdmv_t<T>(ctx, n, T(1), d, w, work0)) return st;
+    const SellCopy* S = a->sell.nslices > 0 ? &a->sell : nullptr;
+    const T* vals = static_cast<const T*>(a->d.val_inner);
+    auto sweep = [&](const T* g, const T* p, T* out, bool pair, bool first, double c0, double c1) {
+        return poly_sweep<T, A>(ctx, S, a->d.A, a->Grb, vals, d, g, p, w, out, pair, first, (T)c0, (T)c1);
+    };
+    // the coefficient that adds root k's own term ahead of its sweep (0: a pair adds its own)
+    auto omega_at = [&](int k) { return im[k] != 0.0 ? 0.0 : 1.0 / re[k]; };
+    T *cur = work0, *oth = work1;
+    bool first = true;
+    for (int k = 0; k < count;) {
+        const bool pair = im[k] != 0.0;
+        const int kn = k + (pair ? 2 : 1);
+        const bool next_ends = kn == count - 1 && im[kn] == 0.0;  // the next root is the final real one
+        if (!pair) {
+            if (kn >= count) break;
+            if (int st = sweep(cur, cur, next_ends ? nullptr : oth, false, first, 1.0 / re[k], omega_at(kn))) return st;
+            T* t = cur;
+            cur = oth;
+            oth = t;
+        } else {
+            const double aa = re[k] * re[k], bb = im[k] * im[k];
+            const double c = 1.0 / (aa + bb);
+            const bool ends = kn >= count;
+            if (int st = sweep(cur, cur, ends ? nullptr : oth, true, first, 2.0 * re[k], c)) return st;
+            if (ends) break;
+            if (int st = sweep(oth, cur, next_ends ? nullptr : cur, false, false, c, omega_at(kn))) return st;
+        }
+        first = false;
+        k = kn;
+    }
+    return MPG_OK;
+}
+
+// ---- the harmonic Ritz values: eigenvalues of an upper Hessenberg matrix ----
+// Shifted QR with Francis double steps on a (n x n, row-major, overwritten),
+// the classical EISPACK organisation: deflate on a negligible subdiagonal
+// entry, take 1 x 1 and 2 x 2 blocks off the bottom, exceptional shifts at
+// iterations 10 and 20 of a block. A 2 x 2 block with discriminant >= 0 gives
+// two real values, else a pair: equal bits of re, im = -+ sqrt(-disc), the
+// member with im < 0 at the lower index. Returns the index whose block did not
+// converge in 60 iterations, or -1.
+int hessenberg_eigenvalues(int n, double* a, double* wr, double* wi) {
+#pragma clang fp contract(off)
+    auto at = [&](int i, int j) -> double& { return a[(size_t)i * n + j]; };
+    double anorm = 0.0;
+    for (int i = 0; i < n; ++i)
+        for (int j = i > 0 ? i - 1 : 0; j < n; ++j) anorm += std::fabs(at(i, j));
+    int nn = n - 1;
+    double t = 0.0, p = 0.0, q = 0.0, r = 0.0;
+    while (nn >= 0) {
+        int its = 0, l;
+        do {
+            for (l = nn; l >= 1; --l) {
+                double s = std::fabs(at(l - 1, l - 1)) + std::fabs(at(l, l));
+                if (s == 0.0) s = anorm;
+                if (std::fabs(at(l, l - 1)) + s == s) {
+                    at(l, l - 1) = 0.0;
+                    break;
+                }
+            }
+            double x = at(nn, nn);
+            if (l == nn) {  // one value
+                wr[nn] = x + t;
+                wi[nn--] = 0.0;
+            } else {
+                double y = at(nn - 1, nn - 1), w = at(nn, nn - 1) * at(nn - 1, nn);
+                if (l == nn - 1) {  // a 2 x 2 block
+                    p = 0.5 * (y - x);
+                    q = p * p + w;
+                    double z = std::sqrt(std::fabs(q));
+                    x += t;
+                    if (q >= 0.0) {
+                        z = p + std::copysign(z, p);
+                        wr[nn - 1] = wr[nn] = x + z;
+                        if (z != 0.0) wr[nn] = x - w / z;
+                        wi[nn - 1] = wi[nn] = 0.0;
+                    } else {
+                        wr[nn - 1] = wr[nn] = x + p;
+                        wi[nn] = z;
+                        wi[nn - 1] = -z;
+                    }
+                    nn -= 2;
+                } else {
+                    if (its == 60) return nn;
+                    if (its == 10 || its == 20) {  // an exceptional shift
+                        t += x;
+                        for (int i = 0; i <= nn; ++i) at(i, i) -= x;
+                        const double s = std::fabs(at(nn, nn - 1)) + std::fabs(at(nn - 1, nn - 2));
+                        y = x = 0.75 * s;
+                        w = -0.4375 * s * s;
+                    }
+                    ++its;
+                    int m;
+                    for (m = nn - 2; m >= l; --m) {  // two consecutive small subdiagonal entries
+                        const double z = at(m, m);
+                        r = x - z;
+                        double s = y - z;
+                        p = (r * s - w) / at(m + 1, m) + at(m, m + 1);
+                        q = at(m + 1, m + 1) - z - r - s;
+                        r = at(m + 2, m + 1);
+                        s = std::fabs(p) + std::fabs(q) + std::fabs(r);
+                        p /= s;
+                        q /= s;
+                        r /= s;
+                        if (m == l) break;
+                        const double u = std::fabs(at(m, m - 1)) * (std::fabs(q) + std::fabs(r));
+                        const double v =
+                            std::fabs(p) * (std::fabs(at(m - 1, m - 1)) + std::fabs(z) + std::fabs(at(m + 1, m + 1)));
+                        if (u + v == v) break;
+                    }
+                    for (int i = m + 2; i <= nn; ++i) {
+                        at(i, i - 2) = 0.0;
+                        if (i != m + 2) at(i, i - 3) = 0.0;
+                    }
+                    for (int k = m; k <= nn - 1; ++k) {  // the double QR step on rows l .. nn, columns m .. nn
+                        if (k != m) {
+                            p = at(k, k - 1);
+                            q = at(k + 1, k - 1);
+                            r = k != nn - 1 ? at(k + 2, k - 1) : 0.0;
+                            x = std::fabs(p) + std::fabs(q) + std::fabs(r);
+                            if (x != 0.0) {
+                                p /= x;
+                                q /= x;
+                                r /= x;
+                            }
+                        }
+                        const double s = std::copysign(std::sqrt(p * p + q * q + r * r), p);
+                        if (s == 0.0) continue;
+                        if (k == m) {
+                            if (l != m) at(k, k - 1) = -at(k, k - 1);
+                        } else {
+                            at(k, k - 1) = -s * x;
+                        }
+                        p += s;
+                        x = p / s;
+                        y = q / s;
+                        const double z = r / s;
+                        q /= p;
+                        r /= p;
+                        for (int j = k; j <= nn; ++j) {
+                            p = at(k, j) + q * at(k + 1, j);
+                            if (k != nn - 1) {
+                                p += r * at(k + 2, j);
+                                at(k + 2, j) -= p * z;
+                            }
+                            at(k + 1, j) -= p * y;
+                            at(k, j) -= p * x;
+                        }
+                        const int mmin = nn < k + 3 ? nn : k + 3;
+                        for (int i = l; i <= mmin; ++i) {
+                            p = x * at(i, k) + y * at(i, k + 1);
+                            if (k != nn - 1) {
+                                p += z * at(i, k + 2);
+                                at(i, k + 2) -= p * r;
+                            }
+                            at(i, k + 1) -= p * q;
+                            at(i, k) -= p;
+                        }
+                    }
+                }
+            }
+        } while (l < nn - 1);
+    }
+    return -1;
 }
 
 // ---- the Gershgorin bound of D A: max_i |d_i| sum_j |a_ij| ----
@@ -405,6 +707,139 @@ int mpg_cheb_coeffs(int steps, double theta, double delta, double* alpha, double
         rho_prev = rho;
     }
     return MPG_OK;
+}
+
+int mpg_csr_poly_sweep_f64(mpg_ctx_t c, mpg_csr_t A, const double* vals, const double* dinv, const double* g,
+                           const double* p, double* z, double* out, int32_t form, int32_t first, int32_t last,
+                           double c0, double c1) {
+    return csr_poly_api<double>(c, A, vals, dinv, g, p, z, out, form, first, last, c0, c1);
+}
+int mpg_csr_poly_sweep_f32(mpg_ctx_t c, mpg_csr_t A, const float* vals, const float* dinv, const float* g,
+                           const float* p, float* z, float* out, int32_t form, int32_t first, int32_t last, float c0,
+                           float c1) {
+    return csr_poly_api<float>(c, A, vals, dinv, g, p, z, out, form, first, last, c0, c1);
+}
+int mpg_sell_poly_sweep_f64(mpg_ctx_t c, mpg_sell_t A, const double* dinv, const double* g, const double* p, double* z,
+                            double* out, int32_t form, int32_t first, int32_t last, double c0, double c1) {
+    return sell_poly_api<double, MPG_F64>(c, A, dinv, g, p, z, out, form, first, last, c0, c1);
+}
+int mpg_sell_poly_sweep_f32(mpg_ctx_t c, mpg_sell_t A, const float* dinv, const float* g, const float* p, float* z,
+                            float* out, int32_t form, int32_t first, int32_t last, float c0, float c1) {
+    return sell_poly_api<float, MPG_F32>(c, A, dinv, g, p, z, out, form, first, last, c0, c1);
+}
+
+// (host arithmetic, here for mpg_cheb_coeffs' reason)
+int mpg_gmres_poly_roots(int s, const double* H, int ldh, double* re, double* im, int* count) {
+#pragma clang fp contract(off)
+    if (count) *count = 0;
+    if (s < 1 || s > 64 || !H || ldh < s || !re || !im || !count) return MPG_ERR_ARG;
+    const int n = s;
+    double G[64 * 64], L[64 * 64], f[64], wr[64], wi[64];
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) G[i * n + j] = j + 1 >= i ? H[(size_t)i * ldh + j] : 0.0;
+    const double h = H[(size_t)n * ldh + (n - 1)];
+    if (!std::isfinite(h)) return MPG_ERR_ARG;
+    if (h != 0.0) {
+        // H_s^T f = e_s by elimination with partial pivoting (L holds H_s^T; ties to the lower row)
+        for (int i = 0; i < n; ++i) {
+            for (int j = 0; j < n; ++j) L[i * n + j] = G[j * n + i];
+            f[i] = i == n - 1 ? 1.0 : 0.0;
+        }
+        for (int k = 0; k < n; ++k) {
+            int piv = k;
+            for (int i = k + 1; i < n; ++i)
+                if (std::fabs(L[i * n + k]) > std::fabs(L[piv * n + k])) piv = i;
+            if (!(std::fabs(L[piv * n + k]) > 0.0) || !std::isfinite(L[piv * n + k])) return MPG_ERR_BREAKDOWN;
+            if (piv != k) {
+                for (int j = 0; j < n; ++j) std::swap(L[k * n + j], L[piv * n + j]);
+                std::swap(f[k], f[piv]);
+            }
+            for (int i = k + 1; i < n; ++i) {
+                const double m = L[i * n + k] / L[k * n + k];
+                if (m == 0.0) continue;
+                for (int j = k; j < n; ++j) L[i * n + j] -= m * L[k * n + j];
+                f[i] -= m * f[k];
+            }
+        }
+        for (int i = n - 1; i >= 0; --i) {
+            double v = f[i];
+            for (int j = i + 1; j < n; ++j) v -= L[i * n + j] * f[j];
+            f[i] = v / L[i * n + i];
+        }
+        const double h2 = h * h;
+        for (int i = 0; i < n; ++i) G[i * n + (n - 1)] += h2 * f[i];
+    }
+    for (int i = 0; i < n * n; ++i)
+        if (!std::isfinite(G[i])) return MPG_ERR_BREAKDOWN;
+    const int bad = hessenberg_eigenvalues(n, G, wr, wi);
+    if (bad >= 0) {
+        *count = bad;
+        return MPG_ERR_BREAKDOWN;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(wr[i]) || !std::isfinite(wi[i]) || (wr[i] == 0.0 && wi[i] == 0.0)) {
+            *count = i;
+            return MPG_ERR_BREAKDOWN;
+        }
+    // Leja order over the items (a real value, or a pair taken as its im > 0 member and standing for both)
+    int item[64], nitems = 0;
+    for (int i = 0; i < n; ++i) {
+        item[nitems++] = i;
+        if (wi[i] != 0.0) ++i;  // (its conjugate follows)
+    }
+    bool used[64] = {};
+    double pr[64], pi[64];  // the members placed
+    int placed = 0;
+    while (placed < n) {
+        int best = -1;
+        double best_score = 0.0;
+        for (int q = 0; q < nitems; ++q) {
+            if (used[q]) continue;
+            const double a = wr[item[q]], b = std::fabs(wi[item[q]]);
+            double score = 0.0;
+            if (placed == 0) score = std::hypot(a, b);
+            else
+                for (int j = 0; j < placed; ++j) score += std::log(std::hypot(a - pr[j], b - pi[j]));
+            if (best < 0 || score > best_score) {
+                best = q;
+                best_score = score;
+            }
+        }
+        used[best] = true;
+        const double a = wr[item[best]], b = std::fabs(wi[item[best]]);
+        pr[placed] = a;
+        pi[placed++] = b;
+        if (b != 0.0) {
+            pr[placed] = a;
+            pi[placed++] = -b;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        re[i] = pr[i];
+        im[i] = pi[i];
+    }
+    *count = n;
+    return MPG_OK;
+}
+
+int mpg_arnoldi_poly_apply(mpg_arnoldi_t a, int32_t count, const double* re, const double* im, void* w, void* work0,
+                           void* work1) {
+    if (!a || !a->ctx || count < 1 || count > 64 || !w || (count >= 2 && !work0) || (count >= 3 && !work1) ||
+        (count >= 2 && work0 == w) || (count >= 3 && (work1 == w || work1 == work0)) || !a->d.diag ||
+        !poly_roots_ok(count, re, im))
+        return MPG_ERR_ARG;
+    // (mpg_arnoldi_neumann_apply's combinations)
+    if ((a->combo != 0 && a->combo != 2 && a->combo != 3) || a->front != 0 || a->d.n_ext != a->d.n)
+        return MPG_ERR_UNSUPPORTED;
+    if (a->d.n == 0) return MPG_OK;
+    if (a->combo == 0)
+        return poly_run<double, double>(a, count, re, im, static_cast<double*>(w), static_cast<double*>(work0),
+                                        static_cast<double*>(work1));
+    if (a->acc32)
+        return poly_run<float, float>(a, count, re, im, static_cast<float*>(w), static_cast<float*>(work0),
+                                      static_cast<float*>(work1));
+    return poly_run<float, double>(a, count, re, im, static_cast<float*>(w), static_cast<float*>(work0),
+                                   static_cast<float*>(work1));
 }
 
 int mpg_arnoldi_neumann_apply(mpg_arnoldi_t a, int32_t steps, void* w, void* work0, void* work1) {

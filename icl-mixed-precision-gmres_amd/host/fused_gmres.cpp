@@ -154,7 +154,13 @@ struct FusedEngine::Impl {
     // interval read at set-up
     bool cheb = false;
     ChebInterval cheb_iv{};
-    bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || (nm_asked == 1 && !cheb); }
+    // GMRES polynomial (prec gmres_poly): again that slot and those vectors,
+    // through mpg_arnoldi_poly_apply on the roots of the set-up (nm_steps =
+    // nm_asked = their count, which an invariant subspace makes smaller than
+    // jacobi_steps; one root is Jacobi scaled by 1 / theta)
+    bool poly = false;
+    PolyRoots poly_roots{};
+    bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || (nm_asked == 1 && !cheb && !poly); }
     bool orthloss = false;    // LostOrthogonality: v_{k+1} stored each step, S / u below
     DevMem loss_S, loss_u;    // (m+1) x (m+1) and m+2 of T, zero-filled (IterUtil.hpp:185-191)
 
@@ -201,6 +207,10 @@ struct FusedEngine::Impl {
     // Jacobi, the Jacobi sweeps, or ILU with typesafe_apply's casts when the preconditioner
     // precision differs (gmres.cpp:12-22)
     void apply_neumann(void* w) {
+        if (poly)
+            return check(mpg_arnoldi_poly_apply(arn, poly_roots.count, poly_roots.re, poly_roots.im, w, nm_work0.p,
+                                                nm_work1.p),
+                         "GMRES-polynomial apply", ctx);
         if (cheb)
             return check(mpg_arnoldi_cheb_apply(arn, nm_steps, cheb_iv.theta(), cheb_iv.delta(), w, nm_work0.p,
                                                 nm_work1.p),
@@ -317,7 +327,7 @@ void FusedEngine::Impl::resolve_policy() {
     if (int st = plan_cycle(P, cycle))
         throw StatusError(st, "MPG_STEP_DOTS=2 / MPG_FUSE_DOTS=2: a step of the cycle cannot take the required SpMV + "
                               "dots launch (one GPU, plain CGS with in-launch sums, no preconditioner launch -- ILU, "
-                              "block Jacobi, Jacobi or Chebyshev sweeps -- between the SpMV and the dots, storage the "
+                              "block Jacobi, Jacobi, Chebyshev or GMRES-polynomial sweeps -- between the SpMV and the dots, storage the "
                               "launch supports)");
 }
 
@@ -341,20 +351,22 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
         throw std::invalid_argument("ILU / ILU-Jacobi factor the whole matrix: not available on a row-partitioned solve");
     const bool bjacobi = a.prec == MPG_PREC_BLOCK_JACOBI;
     const bool chebyshev = a.prec == MPG_PREC_CHEBYSHEV;
-    const bool neumann = a.prec == MPG_PREC_NEUMANN || chebyshev;  // (the sweeps' set-up, whichever polynomial)
+    const bool gmres_poly = a.prec == MPG_PREC_GMRES_POLY;
+    const bool neumann = a.prec == MPG_PREC_NEUMANN || chebyshev || gmres_poly;  // (the sweeps' set-up, whichever polynomial)
     if (!ilu && !bjacobi && !neumann && a.prec != MPG_PREC_IDENTITY && a.prec != MPG_PREC_JACOBI)
         throw std::invalid_argument("Unknown prec type");
     if (neumann) {
-        chebyshev ? check_cheb_args(a) : check_neumann_args(a);
+        gmres_poly ? check_gmres_poly_args(a) : chebyshev ? check_cheb_args(a) : check_neumann_args(a);
         if (comm)
             throw StatusError(MPG_ERR_UNSUPPORTED,
-                              std::string("prec ") + (chebyshev ? "chebyshev" : "neumann") +
+                              std::string("prec ") + (gmres_poly ? "gmres_poly" : chebyshev ? "chebyshev" : "neumann") +
                                   " is not available on a row-partitioned solve: every sweep needs a halo "
                                   "exchange of z (the follow-up that would make it the first preconditioner stronger "
                                   "than Jacobi on more than one GPU)");
         I.cheb = chebyshev;
+        I.poly = gmres_poly;
         I.nm_asked = a.jacobi_steps;
-        I.nm_steps = a.jacobi_steps > 1 || chebyshev ? a.jacobi_steps : 0;
+        I.nm_steps = a.jacobi_steps > 1 || chebyshev || gmres_poly ? a.jacobi_steps : 0;
     }
     if (bjacobi) {
         const int bs = a.prec_block == 0 ? 3 : a.prec_block;
@@ -460,6 +472,16 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
         });
         double al[64], be[64];
         cheb_coefficients(I.nm_steps, I.cheb_iv, al, be);  // (refused here, not at the first application)
+    }
+
+    if (I.poly) {
+        // the roots, from the Arnoldi steps on D A with the matrix the sweeps run on (P = T = its value type)
+        I.poly_roots = ty.P == MPG_F64
+                           ? gmres_poly_setup<double>(ctx, I.csr, static_cast<const double*>(I.val_inner),
+                                                      I.diag.as<double>(), I.n, a.jacobi_steps)
+                           : gmres_poly_setup<float>(ctx, I.csr, static_cast<const float*>(I.val_inner),
+                                                     I.diag.as<float>(), I.n, a.jacobi_steps);
+        I.nm_asked = I.nm_steps = I.poly_roots.count;
     }
 
     // block Jacobi in the preconditioner precision, from the matrix Jacobi<P>
@@ -1003,9 +1025,15 @@ double FusedEngine::phase_bytes(int which) const {
     // the Jacobi sweeps' launches after the SpMV: the gdmv (w read, z written,
     // the diagonal), then per sweep the matrix again, z read and written and
     // three more n-vectors (r, the diagonal, z's own entry); a Chebyshev sweep
-    // after the first reads z_prev too
+    // after the first reads z_prev too. A GMRES-polynomial sweep: the gathered
+    // vector, the diagonal and p read, z read and written, the second output
+    // written (six n-vectors), less z's read in the first sweep and the second
+    // output in the last: with k roots (k - 1) * 6 - 2 n-vectors beside the
+    // matrix, k >= 2
     const double nm = I.nm_steps ? (2 * sT + sP) * n + (I.nm_steps - 1) * (z * (sV + 4) + (n + 1) * 4 + 5 * n * sT) +
-                                       (I.cheb && I.nm_steps > 2 ? (I.nm_steps - 2) * n * sT : 0.0)
+                                       (I.cheb && I.nm_steps > 2 ? (I.nm_steps - 2) * n * sT : 0.0) +
+                                       (I.poly && I.nm_steps > 2 ? (I.nm_steps - 3) * n * sT : 0.0) -
+                                       (I.poly && I.nm_steps == 2 ? n * sT : 0.0)
                                  : 0.0;
     if (which == 0) {
         // SURVEY §8(d) B_spmv, the same for every storage: CSR values + int32
@@ -1051,6 +1079,14 @@ mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
 int FusedEngine::prec_fused() const { return p_->bj_bs ? (p_->bj_fused_step ? 1 : 0) : -1; }
 int FusedEngine::prec_sweeps() const { return p_->nm_asked ? p_->nm_asked : -1; }
+int FusedEngine::prec_roots(double* re, double* im, int cap) const {
+    if (!p_->poly) return -1;
+    for (int i = 0; i < p_->poly_roots.count && i < cap; ++i) {
+        if (re) re[i] = p_->poly_roots.re[i];
+        if (im) im[i] = p_->poly_roots.im[i];
+    }
+    return p_->poly_roots.count;
+}
 bool FusedEngine::prec_interval(double* a, double* b) const {
     if (!p_->cheb) return false;
     if (a) *a = p_->cheb_iv.a;
@@ -1191,6 +1227,9 @@ int mpg_engine_sell_columns(mpg_engine_t e, int32_t* form, int64_t* csr_slices, 
 
 int mpg_engine_prec_fused(mpg_engine_t e) { return e && e->eng ? e->eng->prec_fused() : -1; }
 int mpg_engine_prec_sweeps(mpg_engine_t e) { return e && e->eng ? e->eng->prec_sweeps() : -1; }
+int mpg_engine_prec_roots(mpg_engine_t e, double* re, double* im, int32_t cap) {
+    return e && e->eng ? e->eng->prec_roots(re, im, cap) : -1;
+}
 int mpg_engine_prec_interval(mpg_engine_t e, double* a, double* b) {
     return e && e->eng && e->eng->prec_interval(a, b) ? 0 : -1;
 }

@@ -29,7 +29,8 @@
 
 namespace mpg {
 
-// prec neumann and prec chebyshev (MPG_PREC_NEUMANN, MPG_PREC_CHEBYSHEV; `name`
+// prec neumann, prec chebyshev and prec gmres_poly (MPG_PREC_NEUMANN,
+// MPG_PREC_CHEBYSHEV, MPG_PREC_GMRES_POLY; `name`
 // in the messages): the sweep count and the modes they run in,
 // checked by both engines before any set-up. The sweeps run in the Arnoldi
 // precision on the Arnoldi matrix, so the preconditioner precision has to be
@@ -49,6 +50,7 @@ inline void check_sweep_prec_args(const mpg_solve_args& a, const std::string& na
 }
 inline void check_neumann_args(const mpg_solve_args& a) { check_sweep_prec_args(a, "neumann"); }
 inline void check_cheb_args(const mpg_solve_args& a) { check_sweep_prec_args(a, "chebyshev"); }
+inline void check_gmres_poly_args(const mpg_solve_args& a) { check_sweep_prec_args(a, "gmres_poly"); }
 
 // Communication seam of the row-partitioned solve: a single-GPU engine has
 // no communicator; a multi-GPU rank supplies one (see comm.hpp).
@@ -150,6 +152,7 @@ public:
     int prec_fused() const;  // mpg_engine_prec_fused
     int prec_sweeps() const;  // mpg_engine_prec_sweeps
     bool prec_interval(double* a, double* b) const;  // mpg_engine_prec_interval
+    int prec_roots(double* re, double* im, int cap) const;  // mpg_engine_prec_roots
     int cgs_stream_steps() const;      // CGS update launches of a cycle that take the streaming form
     int step_dots_steps() const;       // steps of a cycle that run the SpMV inside the dots' launch
     bool givens_rider() const;         // ... and one of them folds the Givens step (k_step_dots' rider workgroup)

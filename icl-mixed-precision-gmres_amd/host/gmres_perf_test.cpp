@@ -18,7 +18,9 @@
 // [--cheb-ratio R] [--cheb-lmax L] (the Chebyshev polynomial of S sweeps for a
 // spectrum of D A near [b / R, b]: R > 1, default 30; b = L > 0, default the
 // Gershgorin bound; the two flags set MPG_CHEB_RATIO / MPG_CHEB_LMAX for this
-// process), --device D, --stop-on-breakdown (end the solve with an error at the first
+// process), --prec gmres_poly [--jacobi-steps S] (the GMRES polynomial of D A
+// from S Arnoldi steps run once at set-up: S roots, no interval and no
+// setting), --device D, --stop-on-breakdown (end the solve with an error at the first
 // non-finite Arnoldi residual; without it the count goes to stderr),
 // --ngpus N (row-partition the fused solve over N GPUs of this process, one
 // host thread per GPU, RCCL clique by ncclCommInitAll: mpg_solve_multi_gpu;
@@ -119,6 +121,7 @@ int main(int argc, char* argv[]) {
             else if (v == "bjacobi") a.prec = MPG_PREC_BLOCK_JACOBI;
             else if (v == "neumann") a.prec = MPG_PREC_NEUMANN;
             else if (v == "chebyshev") a.prec = MPG_PREC_CHEBYSHEV;
+            else if (v == "gmres_poly") a.prec = MPG_PREC_GMRES_POLY;
             else { std::cout << "Unknown Preconditioner" << std::endl; return 1; }
         } else if (f == "--engine") {
             const std::string v = next();

@@ -17,6 +17,7 @@
 
 #include <cassert>
 #include <functional>
+#include <utility>
 
 #include "types.hpp"
 
@@ -282,6 +283,93 @@ public:
             Vect<Type, Device> keep = j & 1 ? work1_ : work0_;
             cheb_sweep(A_, diag_, rhs, (j - 1) & 1 ? work1_ : work0_, j == 1 ? Vect<Type, Device>() : keep,
                        j == steps_ - 1 ? rhs : keep, Type(alpha_[j]), Type(beta_[j]));
+        }
+    }
+};
+
+// backend primitives of the GMRES-polynomial preconditioner, whose residual
+// polynomial is prod (1 - x / theta_i): with B = dinv A, the running product p
+// and the result z (each operation rounded to Type)
+//   poly_step: o = p - omega B g;  z += omega_next o;  out = o
+//   poly_pair: t = 2a p - B p;     z += c t;           out = t
+// g is p for a real root and the pair's t for a pair's second half (where
+// out may be p). first: z is not read, it starts as omega p (step) or 0 p
+// (pair). An empty out: the last form, z alone is stored. out is never g.
+template <class Type, class Device>
+void poly_step(SparseMatrix<Type, Device> A, Vect<Type, Device> dinv, Vect<Type, Device> g, Vect<Type, Device> p,
+               Vect<Type, Device> z, Vect<Type, Device> out, bool first, Type omega, Type omega_next);
+template <class Type, class Device>
+void poly_pair(SparseMatrix<Type, Device> A, Vect<Type, Device> dinv, Vect<Type, Device> p, Vect<Type, Device> z,
+               Vect<Type, Device> out, bool first, Type two_a, Type c);
+
+// The roots of the GMRES polynomial in the order they are applied
+// (mpg_gmres_poly_roots' Leja order, solve.h): `steps` Arnoldi steps on dinv A
+// run once by the backend's set-up, fewer roots where those found an invariant
+// subspace. A host value (set-up only); throws where there is no root.
+struct PolyRoots {
+    int count = 0;
+    double re[64] = {}, im[64] = {};
+};
+template <class Type, class Device>
+PolyRoots gmres_poly_roots(SparseMatrix<Type, Device> A, Vect<Type, Device> dinv, int steps);
+
+// GMRES-polynomial preconditioner (an addition to the reference's set):
+// p(D A) D rhs with 1 - x p(x) = prod (1 - x / theta_i), theta_i the harmonic
+// Ritz values of `steps` Arnoldi steps on D A, D Jacobi's inverse diagonal of
+// A_diag, the sweeps on A (as Neumann above). The constructor runs the
+// set-up; the coefficients are host constants rounded once to Type, so apply
+// reads nothing on the host.
+template <class Type, class Device>
+class GmresPoly : public LinearOperator<Type, Device> {
+    SparseMatrix<Type, Device> A_;
+    Vect<Type, Device> diag_, work0_, work1_;
+    PolyRoots roots_;
+
+    double omega_at(int k) const { return roots_.im[k] != 0.0 ? 0.0 : 1.0 / roots_.re[k]; }
+
+public:
+    GmresPoly(SparseMatrix<Type, Device> A_diag, SparseMatrix<Type, Device> A, int steps) : A_(A), diag_(A.nrows()) {
+        jacobi_diag(A_diag, diag_);
+        roots_ = gmres_poly_roots(A_, diag_, steps);
+        if (roots_.count >= 2) work0_ = Vect<Type, Device>(A.nrows());
+        if (roots_.count >= 3) work1_ = Vect<Type, Device>(A.nrows());
+    }
+    int n() const { return (int)diag_.n(); }
+    int steps() const { return roots_.count; }
+    const PolyRoots& roots() const { return roots_; }
+    Vect<Type, Device> diag_vect() { return diag_; }
+    // p_0 = D rhs into work0 (one root: (1 / theta) D rhs in place), z in rhs
+    // from the first sweep on. A real root that is not the last: one step,
+    // the new p into the other work vector. A pair: its first half stores t
+    // there, its second half (unless the pair ends the list) gathers t and
+    // stores the new p over the current one. A final real root's term came
+    // with the sweep before it.
+    void apply(Vect<Type, Device> rhs) override {
+        const int count = roots_.count;
+        const double *re = roots_.re, *im = roots_.im;
+        if (count == 1) return gdmv(Type(1.0 / re[0]), diag_, rhs, Type(0), rhs);
+        gdmv(Type(1), diag_, rhs, Type(0), work0_);
+        Vect<Type, Device> cur = work0_, oth = work1_, none;
+        bool first = true;
+        for (int k = 0; k < count;) {
+            const bool pair = im[k] != 0.0;
+            const int kn = k + (pair ? 2 : 1);
+            const bool next_ends = kn == count - 1 && im[kn] == 0.0;
+            if (!pair) {
+                if (kn >= count) break;
+                poly_step(A_, diag_, cur, cur, rhs, next_ends ? none : oth, first, Type(1.0 / re[k]),
+                          Type(omega_at(kn)));
+                std::swap(cur, oth);
+            } else {
+                const double aa = re[k] * re[k], bb = im[k] * im[k];
+                const double c = 1.0 / (aa + bb);
+                const bool ends = kn >= count;
+                poly_pair(A_, diag_, cur, rhs, ends ? none : oth, first, Type(2.0 * re[k]), Type(c));
+                if (ends) break;
+                poly_step(A_, diag_, oth, cur, rhs, next_ends ? none : cur, false, Type(c), Type(omega_at(kn)));
+            }
+            first = false;
+            k = kn;
         }
     }
 };

@@ -18,6 +18,7 @@
 
 #include "kernels.hpp"
 #include "mpgmres/arnoldi.h"  // mpg_dtype_t
+#include "mpgmres/problems.h"  // mpg_rand_vect
 #include "mpgmres/solve.h"
 
 namespace mpg {
@@ -1243,6 +1244,144 @@ void cheb_coefficients(int steps, const ChebInterval& iv, double* alpha, double*
         throw mpg::StatusError(st, os.str());
     }
 }
+
+// one sweep of the GMRES polynomial, on the storage jacobi_sweep takes
+namespace {
+template <class T, class CsrFn, class SellFn>
+void poly_sweep_hip(CsrFn csr_fn, SellFn sell_fn, SparseMatrix<T, Hip>& A, Vect<T, Hip>& d, Vect<T, Hip>& g,
+                    Vect<T, Hip>& p, Vect<T, Hip>& z, Vect<T, Hip>& out, int form, bool first, T c0, T c1) {
+    assert(A.nrows() == A.ncols() && !A.is_transposed() && (size_t)A.nrows() == p.n() && d.n() == p.n() &&
+           g.n() == p.n() && z.n() == p.n() && (out.n() == 0 || out.n() == p.n()));
+    mpg_sell_t s = A.node() ? nullptr : A.sell();
+    const int last = out.n() == 0;
+    check(s ? sell_fn(C, s, d.data(), g.data(), p.data(), z.data(), out.data(), form, first, last, c0, c1)
+            : csr_fn(C, A.csr(), A.vals_data(), d.data(), g.data(), p.data(), z.data(), out.data(), form, first, last,
+                     c0, c1),
+          "GMRES-polynomial sweep");
+}
+}  // namespace
+template <> void poly_step<double, Hip>(SparseMatrix<double, Hip> A, Vect<double, Hip> d, Vect<double, Hip> g,
+                                        Vect<double, Hip> p, Vect<double, Hip> z, Vect<double, Hip> out, bool first,
+                                        double omega, double omega_next) {
+    poly_sweep_hip<double>(mpg_csr_poly_sweep_f64, mpg_sell_poly_sweep_f64, A, d, g, p, z, out, MPG_POLY_STEP, first,
+                           omega, omega_next);
+}
+template <> void poly_step<float, Hip>(SparseMatrix<float, Hip> A, Vect<float, Hip> d, Vect<float, Hip> g,
+                                       Vect<float, Hip> p, Vect<float, Hip> z, Vect<float, Hip> out, bool first,
+                                       float omega, float omega_next) {
+    poly_sweep_hip<float>(mpg_csr_poly_sweep_f32, mpg_sell_poly_sweep_f32, A, d, g, p, z, out, MPG_POLY_STEP, first,
+                          omega, omega_next);
+}
+template <> void poly_pair<double, Hip>(SparseMatrix<double, Hip> A, Vect<double, Hip> d, Vect<double, Hip> p,
+                                        Vect<double, Hip> z, Vect<double, Hip> out, bool first, double two_a,
+                                        double c) {
+    poly_sweep_hip<double>(mpg_csr_poly_sweep_f64, mpg_sell_poly_sweep_f64, A, d, p, p, z, out, MPG_POLY_PAIR, first,
+                           two_a, c);
+}
+template <> void poly_pair<float, Hip>(SparseMatrix<float, Hip> A, Vect<float, Hip> d, Vect<float, Hip> p,
+                                       Vect<float, Hip> z, Vect<float, Hip> out, bool first, float two_a, float c) {
+    poly_sweep_hip<float>(mpg_csr_poly_sweep_f32, mpg_sell_poly_sweep_f32, A, d, p, p, z, out, MPG_POLY_PAIR, first,
+                          two_a, c);
+}
+template <> PolyRoots gmres_poly_roots<double, Hip>(SparseMatrix<double, Hip> A, Vect<double, Hip> d, int steps) {
+    return mpg::gmres_poly_setup<double>(C, A.csr(), A.vals_data(), d.data(), (int64_t)A.nrows(), steps);
+}
+template <> PolyRoots gmres_poly_roots<float, Hip>(SparseMatrix<float, Hip> A, Vect<float, Hip> d, int steps) {
+    return mpg::gmres_poly_setup<float>(C, A.csr(), A.vals_data(), d.data(), (int64_t)A.nrows(), steps);
+}
+
+namespace mpg {
+namespace {
+struct DevBuf {  // device memory of the set-up, freed on every way out
+    mpg_ctx_t ctx;
+    void* p = nullptr;
+    DevBuf(mpg_ctx_t c, size_t bytes) : ctx(c) { check(mpg_malloc(c, bytes ? bytes : 8, &p), "mpg_malloc", c); }
+    ~DevBuf() { mpg_free(ctx, p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+};
+template <class T> struct PolyOps;
+template <> struct PolyOps<double> {
+    static constexpr auto spmv = mpg_csr_spmv_f64;
+    static constexpr auto gdmv = mpg_gdmv_f64;
+    static constexpr auto axpy = mpg_axpy_f64;
+    static constexpr auto scal = mpg_scal_f64;
+    static constexpr auto dot = mpg_dot_acc_f64;
+};
+template <> struct PolyOps<float> {
+    static constexpr auto spmv = mpg_csr_spmv_f32;
+    static constexpr auto gdmv = mpg_gdmv_f32;
+    static constexpr auto axpy = mpg_axpy_f32;
+    static constexpr auto scal = mpg_scal_f32;
+    static constexpr auto dot = mpg_dot_acc_f32;
+};
+}  // namespace
+
+template <class T>
+PolyRoots gmres_poly_setup(mpg_ctx_t ctx, mpg_csr_t A, const T* vals, const T* dinv, int64_t n, int steps) {
+    using O = PolyOps<T>;
+    if (steps < 1 || steps > 64) throw StatusError(MPG_ERR_ARG, "prec gmres_poly: the step count is outside [1, 64]");
+    const size_t nn = (size_t)n;
+    DevBuf basis(ctx, (size_t)(steps + 1) * nn * sizeof(T)), tmp(ctx, nn * sizeof(T)), acc(ctx, sizeof(double));
+    T* V = static_cast<T*>(basis.p);
+    T* t = static_cast<T*>(tmp.p);
+    double* acc_dev = static_cast<double*>(acc.p);
+    auto dot = [&](const T* x, const T* y) {
+        double v = 0.0;
+        check(O::dot(ctx, n, x, y, acc_dev), "prec gmres_poly: dot", ctx);
+        check(mpg_memcpy_d2h(ctx, &v, acc_dev, sizeof(double)), "prec gmres_poly: dot", ctx);
+        return v;
+    };
+    {  // v_0 = D g, g = T(u) - T(0.5)
+        std::vector<double> u(nn);
+        check(mpg_rand_vect(n, 1, u.data()), "mpg_rand_vect");
+        std::vector<T> g(nn);
+        for (size_t i = 0; i < nn; ++i) g[i] = T(u[i]) - T(0.5);
+        check(mpg_memcpy_h2d(ctx, t, g.data(), nn * sizeof(T)), "prec gmres_poly: start vector", ctx);
+        check(O::gdmv(ctx, n, T(1), dinv, t, T(0), V), "prec gmres_poly: start vector", ctx);
+    }
+    const double beta = std::sqrt(dot(V, V));
+    if (!(std::isfinite(beta) && beta > 0.0)) {
+        std::ostringstream os;
+        os << "prec gmres_poly: the start vector D g has norm " << beta << ": no Arnoldi step, no root";
+        throw StatusError(MPG_ERR_BREAKDOWN, os.str());
+    }
+    check(O::scal(ctx, n, T(1.0 / beta), V), "prec gmres_poly: scal", ctx);
+    std::vector<double> H((size_t)(steps + 1) * steps, 0.0);
+    int k = 0;  // completed steps whose subdiagonal entry is usable
+    for (; k < steps; ++k) {
+        T* w = V + (size_t)(k + 1) * nn;
+        check(O::spmv(ctx, A, T(1), vals, V + (size_t)k * nn, T(0), t), "prec gmres_poly: SpMV", ctx);
+        check(O::gdmv(ctx, n, T(1), dinv, t, T(0), w), "prec gmres_poly: diagonal", ctx);
+        for (int j = 0; j <= k; ++j) {  // MGS
+            const double h = dot(V + (size_t)j * nn, w);
+            H[(size_t)j * steps + k] = h;
+            check(O::axpy(ctx, n, T(-h), V + (size_t)j * nn, w), "prec gmres_poly: axpy", ctx);
+        }
+        const double hk = std::sqrt(dot(w, w));
+        H[(size_t)(k + 1) * steps + k] = hk;
+        if (!(std::isfinite(hk) && hk > 0.0)) {  // an invariant subspace: the Ritz values of H_{k+1}
+            H[(size_t)(k + 1) * steps + k] = 0.0;
+            ++k;
+            break;
+        }
+        if (k + 1 < steps) check(O::scal(ctx, n, T(1.0 / hk), w), "prec gmres_poly: scal", ctx);
+    }
+    PolyRoots r;
+    const int st = mpg_gmres_poly_roots(k, H.data(), steps, r.re, r.im, &r.count);
+    if (st) {
+        std::ostringstream os;
+        os << "prec gmres_poly: no roots from " << k << " Arnoldi steps on D A";
+        if (st == MPG_ERR_BREAKDOWN)
+            os << " (harmonic Ritz value " << r.count << " is zero, not finite or did not converge)";
+        r.count = 0;
+        throw StatusError(st, os.str());
+    }
+    return r;
+}
+template PolyRoots gmres_poly_setup<double>(mpg_ctx_t, mpg_csr_t, const double*, const double*, int64_t, int);
+template PolyRoots gmres_poly_setup<float>(mpg_ctx_t, mpg_csr_t, const float*, const float*, int64_t, int);
+}  // namespace mpg
 
 // ---- ILU(0) / ILU-Jacobi (kernels_mkl.cpp:355-506, kernels_cuda.cpp:617-791) ----
 namespace {

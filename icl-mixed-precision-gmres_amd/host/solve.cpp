@@ -44,8 +44,8 @@ std::unique_ptr<Convergence<T, Hip>> make_convergence(const mpg_solve_args& a) {
 
 // gmres_perf_test.cpp:69-89, 139-159 (ILU from the fp64 A; Jacobi from A
 // converted to the preconditioner precision). inner: the matrix the Arnoldi
-// cycle runs on when it is held in P (prec neumann and prec chebyshev sweep on
-// it), else nullptr.
+// cycle runs on when it is held in P (prec neumann, prec chebyshev and prec
+// gmres_poly sweep on it), else nullptr.
 template <class P>
 std::unique_ptr<LinearOperator<P, Hip>> make_preconditioner(int prec, const SparseMatrix<double, Hip>& A,
                                                             int jacobi_steps, int prec_block,
@@ -62,6 +62,12 @@ std::unique_ptr<LinearOperator<P, Hip>> make_preconditioner(int prec, const Spar
                 throw StatusError(MPG_ERR_UNSUPPORTED, "prec chebyshev needs the Arnoldi matrix in the preconditioner "
                                                        "precision");
             return std::make_unique<Chebyshev<P, Hip>>(SparseMatrix<P, Hip>(A), *inner, jacobi_steps);
+        }
+        case MPG_PREC_GMRES_POLY: {
+            if (!inner)
+                throw StatusError(MPG_ERR_UNSUPPORTED, "prec gmres_poly needs the Arnoldi matrix in the preconditioner "
+                                                       "precision");
+            return std::make_unique<GmresPoly<P, Hip>>(SparseMatrix<P, Hip>(A), *inner, jacobi_steps);
         }
         case MPG_PREC_BLOCK_JACOBI: {
             const int bs = prec_block == 0 ? 3 : prec_block;
@@ -206,6 +212,7 @@ void dispatch_mode(const mpg_solve_args& a, const SparseMatrix<double, Hip>& A, 
 int solve_surface(const mpg_solve_args& a, mpg_solve_result* r) {
     if (a.prec == MPG_PREC_NEUMANN) check_neumann_args(a);
     if (a.prec == MPG_PREC_CHEBYSHEV) check_cheb_args(a);
+    if (a.prec == MPG_PREC_GMRES_POLY) check_gmres_poly_args(a);
     SparseMatrix<double, Hip> A(a.n, a.n, a.rowptr, a.col, a.val);
     const size_t n = (size_t)a.n;
     Vect<double, Hip> b(n), xt(n);

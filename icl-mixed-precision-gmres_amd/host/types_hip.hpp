@@ -55,6 +55,20 @@ void set_redirect(mpg_ctx_t c, void* w, void* sp, int64_t n, bool f64);
 bool take_ride(const void* x, const void* y, int64_t n, bool f64, mpg_scalar_op* ops, int& nops, mpg_ctx_t& c,
                int32_t& nparts, void*& h, const void*& w);
 
+// The set-up of prec gmres_poly, the one function both engines call (so both
+// get the same roots): `steps` MGS Arnoldi steps on B = D A from v_0 = D g,
+// g_i = T(u_i) - T(0.5), u = mpg_rand_vect(n, 1) (a zero-mean start: an
+// all-positive one left lap16 unconverged at 2 and 4 steps), through
+// mpg_csr_spmv_*, mpg_gdmv_*, mpg_axpy_* and mpg_scal_* on the CSR arrays,
+// dots accumulated in fp64 (mpg_dot_acc_*, a fixed tree: the same bits every
+// time) and kept in fp64 as H; then mpg_gmres_poly_roots. A step k < steps
+// that ends with h_{k+1,k} zero or not finite keeps the first k roots (the
+// Ritz values of the invariant subspace). Throws StatusError
+// (MPG_ERR_BREAKDOWN) for k = 0 and for a root the library refuses, naming it.
+// vals, dinv: n-row device arrays of T = float or double. Reads on the host.
+template <class T>
+PolyRoots gmres_poly_setup(mpg_ctx_t ctx, mpg_csr_t A, const T* vals, const T* dinv, int64_t n, int steps);
+
 // The calling thread's current HIP context (stream + workspace). Created
 // lazily on the device named by MPG_DEVICE (default 0) unless a
 // ScopedContext installed one.

@@ -119,6 +119,25 @@ int mpg_arnoldi_neumann_apply(mpg_arnoldi_t a, int32_t steps, void* w, void* wor
  * mpg_arnoldi_neumann_apply; MPG_ERR_ARG also unless 0 < delta < theta, finite. */
 int mpg_arnoldi_cheb_apply(mpg_arnoldi_t a, int32_t steps, double theta, double delta, void* w, void* work0,
                            void* work1);
+/* The GMRES-polynomial preconditioner (MPG_PREC_GMRES_POLY, solve.h; an
+ * addition to the reference's set) on the workspace's own Arnoldi matrix:
+ * w <- p(D A) D w, 1 - x p(x) = prod_{i < count} (1 - x / (re[i] + i im[i])).
+ * The roots in the order given (mpg_gmres_poly_roots' Leja order): finite,
+ * nonzero, a member with im > 0 followed at once by its conjugate (the same
+ * bits of re, the opposite im). count == 1: mpg_gdmv_*(T(1 / re[0]), D, w, 0, w).
+ * Otherwise mpg_gdmv_*(1, D, w, 0, work0) forms p_0 and count - 1 launches of
+ * mpg_*_poly_sweep_*'s arithmetic (capi.h) in the workspace's accumulation
+ * class follow, z = w throughout: a real root that is not the last is one STEP
+ * (g = p = the current work vector, out = the other one, which becomes
+ * current); a pair is a PAIR (out = the other work vector) and, unless it ends
+ * the list, a STEP that gathers that vector and stores over the current one. A
+ * final real root's term came from the STEP before it; the sweep before the
+ * end is the last form. Coefficients 1 / re, 2 re and 1 / (re^2 + im^2) are
+ * formed in fp64 and rounded once to T. Vectors (work0 from count >= 2, work1
+ * from count >= 3), MPG_ERR_UNSUPPORTED and MPG_ERR_ARG as for
+ * mpg_arnoldi_neumann_apply; MPG_ERR_ARG also for a root list not as above. */
+int mpg_arnoldi_poly_apply(mpg_arnoldi_t a, int32_t count, const double* re, const double* im, void* w, void* work0,
+                           void* work1);
 
 /* Storage the Arnoldi SpMV runs on: *format 1 = CSR row blocks (cuSPARSE
  * csrmv's input, types_cuda.hpp:53-60), 2 = SELL-64 copy made at create

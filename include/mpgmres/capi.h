@@ -504,6 +504,40 @@ int mpg_sell_cheb_sweep_f32(mpg_ctx_t ctx, mpg_sell_t A, const float* dinv, cons
 int mpg_csr_jacobi_bound_f64(mpg_ctx_t ctx, mpg_csr_t A, const double* vals, const double* dinv, double* b_host);
 int mpg_csr_jacobi_bound_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, const float* dinv, double* b_host);
 
+/* ---- GMRES-polynomial sweep (neumann.hip; an addition to the reference's
+ * set): one launch of the product form of MPG_PREC_GMRES_POLY (solve.h), whose
+ * residual polynomial is prod_i (1 - x / theta_i). With B = D A, p the running
+ * product (p_0 = D r, mpg_gdmv_*) and z the result, per row i
+ *   s_i = T(sum_j a_ij g[j])      the row sum of mpg_*_jacobi_sweep_* above
+ * form MPG_POLY_STEP, c0 = omega, c1 = omega_next (a real root theta, omega =
+ * 1 / theta; omega_next = 1 / the next root, 0 where that is a pair):
+ *   u = dinv[i] * s_i;  v = c0 * u;  o = p[i] - v;  y = c1 * o
+ *   z[i] = z[i] + y;  out[i] = o
+ * form MPG_POLY_PAIR, the first half of a pair a +- b i, c0 = 2 a, c1 =
+ * 1 / (a^2 + b^2):
+ *   u = dinv[i] * s_i;  q = c0 * p[i];  t = q - u;  y = c1 * t
+ *   z[i] = z[i] + y;  out[i] = t
+ * every operation rounded to T (no contraction). A pair's second half is a
+ * STEP with c0 = the pair's c1, g = t and p the vector the first half gathered;
+ * there out may be p (row i's lane alone reads p[i], before its store).
+ * Otherwise g == p. first != 0: z is not read; z[i] is taken as w0 * p[i], w0 =
+ * c0 for a STEP (the first root's own term) and 0 for a PAIR. last != 0: out
+ * must be NULL and only z is stored; with last == 0 out must not be NULL.
+ * MPG_ERR_ARG: as for the Jacobi sweep, another form, out == g, or z equal to
+ * g, p or out. One launch. */
+#define MPG_POLY_STEP 0
+#define MPG_POLY_PAIR 1
+int mpg_csr_poly_sweep_f64(mpg_ctx_t ctx, mpg_csr_t A, const double* vals, const double* dinv, const double* g,
+                           const double* p, double* z, double* out, int32_t form, int32_t first, int32_t last,
+                           double c0, double c1);
+int mpg_csr_poly_sweep_f32(mpg_ctx_t ctx, mpg_csr_t A, const float* vals, const float* dinv, const float* g,
+                           const float* p, float* z, float* out, int32_t form, int32_t first, int32_t last, float c0,
+                           float c1);
+int mpg_sell_poly_sweep_f64(mpg_ctx_t ctx, mpg_sell_t A, const double* dinv, const double* g, const double* p,
+                            double* z, double* out, int32_t form, int32_t first, int32_t last, double c0, double c1);
+int mpg_sell_poly_sweep_f32(mpg_ctx_t ctx, mpg_sell_t A, const float* dinv, const float* g, const float* p, float* z,
+                            float* out, int32_t form, int32_t first, int32_t last, float c0, float c1);
+
 #ifdef __cplusplus
 }
 #endif

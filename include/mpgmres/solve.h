@@ -41,12 +41,17 @@ typedef enum {
     MPG_PREC_NEUMANN = 5, /* new: jacobi_steps Jacobi sweeps on A z = r from z = 0, the truncated Neumann series
                              sum_{j<s} (I - D A)^j D with Jacobi's D (mpg_*_jacobi_sweep_*, capi.h); s = 1 is
                              MPG_PREC_JACOBI's bits */
-    MPG_PREC_CHEBYSHEV = 6 /* new: the Chebyshev polynomial of degree jacobi_steps - 1 in D A applied to D r, for a
+    MPG_PREC_CHEBYSHEV = 6, /* new: the Chebyshev polynomial of degree jacobi_steps - 1 in D A applied to D r, for a
                               spectrum of D A near [b / ratio, b] (mpg_*_cheb_sweep_*, capi.h; mpg_cheb_coeffs and
                               mpg_engine_prec_interval below). b: the Gershgorin bound of D A, or MPG_CHEB_LMAX
                               (a real > 0); ratio: MPG_CHEB_RATIO (a real > 1, default 30); both read once when the
                               preconditioner is set up. For spectra on the positive real axis: a banded matrix whose
                               D A has a disc around 1 wants a small ratio, or MPG_PREC_NEUMANN */
+    MPG_PREC_GMRES_POLY = 7 /* new: the GMRES polynomial of D A: p(D A) D r with 1 - x p(x) = prod (1 - x / theta_i),
+                               theta_i the jacobi_steps harmonic Ritz values of jacobi_steps Arnoldi steps on D A run
+                               once at set-up (mpg_gmres_poly_roots and mpg_engine_prec_roots below;
+                               mpg_*_poly_sweep_*, capi.h). No interval and no setting; nonsymmetric spectra give
+                               complex pairs */
 } mpg_prec_t;
 
 typedef enum {
@@ -72,8 +77,8 @@ typedef struct {
     double rtol;           /* --rtol (0: base Convergence) */
     int32_t repeat_iter;   /* --repeat-iter */
     int32_t orthloss;      /* --orthloss */
-    int32_t jacobi_steps;  /* --jacobi-steps: sweeps of MPG_PREC_ILU_JACOBI's solves; MPG_PREC_NEUMANN's and
-                              MPG_PREC_CHEBYSHEV's sweep count s, 1 <= s <= 64 (anything else MPG_ERR_ARG) */
+    int32_t jacobi_steps;  /* --jacobi-steps: sweeps of MPG_PREC_ILU_JACOBI's solves; MPG_PREC_NEUMANN's,
+                              MPG_PREC_CHEBYSHEV's and MPG_PREC_GMRES_POLY's sweep count s, 1 <= s <= 64 (anything else MPG_ERR_ARG) */
     int32_t verbose;       /* print the reference's stdout lines */
     int32_t device;        /* HIP device (mpg_solve only) */
     int32_t threads;       /* host threads (oracle only; 0 = default) */
@@ -213,8 +218,10 @@ int mpg_engine_cgs_stream_steps(mpg_engine_t e);
 /* block Jacobi: 1 when the apply runs inside the SpMV / residual launches, 0 when it is a
  * launch of its own between them and the dots; -1 for every other preconditioner */
 int mpg_engine_prec_fused(mpg_engine_t e);
-/* MPG_PREC_NEUMANN, MPG_PREC_CHEBYSHEV: the sweep count the engine applies per preconditioner application
- * (jacobi_steps: one gdmv launch and that many minus one sweep launches); -1 for every other preconditioner */
+/* MPG_PREC_NEUMANN, MPG_PREC_CHEBYSHEV, MPG_PREC_GMRES_POLY: the sweep count the engine applies per preconditioner
+ * application (jacobi_steps: one gdmv launch and that many minus one sweep launches; for MPG_PREC_GMRES_POLY the
+ * number of roots, smaller than jacobi_steps where the set-up's Arnoldi found an invariant subspace); -1 for every
+ * other preconditioner */
 int mpg_engine_prec_sweeps(mpg_engine_t e);
 /* MPG_PREC_CHEBYSHEV (an addition to the reference's set): the interval [*a, *b] the engine built its
  * coefficients for; returns 0, or -1 for every other preconditioner (a and b untouched) */
@@ -228,6 +235,23 @@ int mpg_engine_prec_interval(mpg_engine_t e, double* a, double* b);
  * alpha, beta: `steps` entries each. Both engines call it and round each value once to the vectors' type.
  * MPG_ERR_ARG: steps outside [1, 64], a NULL array, or not 0 < delta < theta (finite). Host arithmetic only. */
 int mpg_cheb_coeffs(int steps, double theta, double delta, double* alpha, double* beta);
+/* MPG_PREC_GMRES_POLY (an addition to the reference's set): the roots the engine applies, in the order it applies
+ * them. Returns their count (mpg_engine_prec_sweeps' value) and stores the first min(count, cap) into re / im
+ * (either may be NULL with cap == 0); -1 for every other preconditioner. */
+int mpg_engine_prec_roots(mpg_engine_t e, double* re, double* im, int32_t cap);
+/* The GMRES polynomial's roots (an addition to the reference's set) from the (s + 1) x s Hessenberg matrix of s
+ * Arnoldi steps, H[i * ldh + j] = h_{i+1,j+1}, 1 <= s <= 64, ldh >= s: the harmonic Ritz values, that is the
+ * eigenvalues of H_s + h^2 f e_s^T, h = h_{s+1,s}, H_s^T f = e_s solved by elimination with partial pivoting (h == 0:
+ * the eigenvalues of H_s, the Ritz values of an invariant subspace). Eigenvalues by a shifted Hessenberg QR iteration
+ * with Francis double steps, in fp64 without contraction; a 2 x 2 block with discriminant >= 0 gives two real
+ * roots, else a pair with the same bits of re and opposite im. Returned in Leja order: first the root of largest
+ * modulus, then each time the one that maximises sum_j log |theta - theta_j| over the members already placed (both
+ * members of a placed pair); a pair takes two consecutive places, its im > 0 member first; ties go to the root the
+ * iteration stored at the lower index. *count = s. MPG_ERR_ARG: s or ldh out of range, a NULL argument, h not
+ * finite. MPG_ERR_BREAKDOWN: H_s singular to the elimination (with h != 0), the iteration not converged (*count =
+ * the row it stopped at), or a root that is not finite or is zero (*count = its index before ordering). Host
+ * arithmetic only. */
+int mpg_gmres_poly_roots(int s, const double* H, int ldh, double* re, double* im, int* count);
 /* the accumulation class the engine's Arnoldi runs: MPG_ACCUM_F64 0 / MPG_ACCUM_F32 1 (arnoldi.h) */
 int mpg_engine_accum(mpg_engine_t e);
 /* the residual prologue's storage (mpg_arnoldi_prologue_format: 1 CSR, 2 SELL, 3 node blocks) */
@@ -262,7 +286,7 @@ typedef struct {
     int32_t step_dots;    /* MPG_STEP_DOTS: 0 never, 1 wherever supported, 2 required, -1 the steps lo <= k + 1 <= hi */
     int32_t step_dots_lo, step_dots_hi;
     int32_t sep_prec;          /* a preconditioner that is not applied inside the phase kernels (ILU, block Jacobi,
-                                  the Jacobi-sweep and Chebyshev polynomials) */
+                                  the Jacobi-sweep, Chebyshev and GMRES polynomials) */
     int32_t sep_prec_step;     /* ... a launch of its own after every SpMV */
     int32_t sep_prec_prologue; /* ... and after the residual prologue */
     int32_t partials_max_cols; /* mpg_arnoldi_partials_max_cols() */

@@ -1,6 +1,6 @@
 """GMRES it/s with each preconditioner on one MI355X (fused engine, mixed
 CGS GMRES(m), tol = 0, fixed work): identity, Jacobi, the Jacobi-sweep
-polynomial (neumann, 2 and 4 sweeps; chebyshev:2/3/4/6 on request), ILU(0) (sync-free triangular solves) and
+polynomial (neumann, 2 and 4 sweeps; chebyshev:2/3/4/6/8, gmres_poly:4/6/8 and neumann:6/8 on request), ILU(0) (sync-free triangular solves) and
 ILU-Jacobi (5 sweeps), on LAP-1M (the 100^3 7-point Laplacian,
 triangular-solve depth ~ 300) and a BAND matrix (depth = n).
 
@@ -22,7 +22,10 @@ PRECS = {"identity": ("identity", 1), "jacobi": ("jacobi", 1), "neumann:2": ("ne
          "ilu": ("ilu", 1), "ilu_jacobi": ("ilu_jacobi", 5),
          # on request (--precs): the Chebyshev polynomial, its interval from MPG_CHEB_RATIO / MPG_CHEB_LMAX
          "chebyshev:2": ("chebyshev", 2), "chebyshev:3": ("chebyshev", 3), "chebyshev:4": ("chebyshev", 4),
-         "chebyshev:6": ("chebyshev", 6)}
+         "chebyshev:6": ("chebyshev", 6), "chebyshev:8": ("chebyshev", 8),
+         # ... and the GMRES polynomial (no setting), with neumann at the same counts
+         "gmres_poly:4": ("gmres_poly", 4), "gmres_poly:6": ("gmres_poly", 6), "gmres_poly:8": ("gmres_poly", 8),
+         "neumann:6": ("neumann", 6), "neumann:8": ("neumann", 8)}
 DEFAULT_PRECS = "identity,jacobi,neumann:2,neumann:4,ilu,ilu_jacobi"
 
 
