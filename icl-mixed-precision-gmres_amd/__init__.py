@@ -212,6 +212,7 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_cycle_policy.argtypes = [C.c_void_p, C.POINTER(CyclePolicy)]
     lib.mpg_cycle_plan_describe.argtypes = [C.POINTER(CyclePolicy), C.c_char_p, C.c_int]
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
+    lib.mpg_engine_basis.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_fused.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_sweeps.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_interval.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -319,6 +320,11 @@ _HIP_DECLS.update({
     "mpg_arnoldi_create": ([_P, _P, C.POINTER(_P)], C.c_int),
     "mpg_arnoldi_destroy": ([_P], C.c_int),
     "mpg_arnoldi_set_accum": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_set_basis": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_basis": ([_P], C.c_int),
+    "mpg_arnoldi_basis_dev": ([_P, C.POINTER(_I64)], _P),
+    "mpg_arnoldi_givens_spmv": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_sums_dev": ([_P], _P),
     "mpg_arnoldi_spmv": ([_P, C.c_int], C.c_int),
     "mpg_arnoldi_wprev_dev": ([_P, C.c_int], _P),
     "mpg_arnoldi_inv_dev": ([_P], _P),
@@ -557,12 +563,20 @@ class Result:
 def make_args(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, mode="mixed", orth="mgs",
               prec="identity", rlen=30, tol=1e-6, max_restarts=1_000_000, rtol=0.0, repeat_iter=False,
               orthloss=False, jacobi_steps=1, engine="fused", verbose=False, device=0, threads=0,
-              spmv_format="auto", half_unscaled=False, stop_on_breakdown=False, accum="f64", prec_block=3):
+              spmv_format="auto", half_unscaled=False, stop_on_breakdown=False, accum="f64", prec_block=3,
+              basis=None):
     """Build mpg_solve_args (shared by mpg_solve and the CPU oracle).
     accum: the fp32 Arnoldi's accumulation class, "f64" (fp32 products
     summed in fp64, rounded once) or "f32" (every partial sum in fp32: the
     reference's cblas_s* / mkl_sparse_s_mv class; fused engine only).
-    prec_block: unknowns per node of prec="bjacobi" (2, 3 or 4)."""
+    prec_block: unknowns per node of prec="bjacobi" (2, 3 or 4).
+    basis: the fused engine's Krylov basis storage, "f32", "f16" (2 bytes per
+    entry: fp16 of 2^14 v, all arithmetic in the Arnoldi precision; mode
+    mixed, cgs / cgsr, rlen <= 32, one GPU) or "f16emu" (the same values held
+    as fp32; tests). Not a field of mpg_solve_args: it rides on the returned
+    structure and the call that creates the engine runs with the setting
+    MPG_BASIS in its place (mpg_engine_basis, solve.h), restored afterwards.
+    None: the process's own MPG_BASIS, f32 when unset."""
     b = np.ascontiguousarray(b, dtype=np.float64)
     keep = [A.rowptr, A.col, A.val, b]
     a = SolveArgs()
@@ -584,7 +598,29 @@ def make_args(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, mod
     a.stop_on_breakdown = int(stop_on_breakdown)
     a.accum = ACCUMS[accum]
     a.prec_block = prec_block
+    a._basis = None if basis is None else str(basis)
     return a, keep
+
+
+class _basis_setting:
+    """MPG_BASIS = args' basis around the call that creates an engine (the
+    setting is read once there); the process's own value is put back."""
+
+    def __init__(self, args):
+        self.basis = getattr(args, "_basis", None)
+
+    def __enter__(self):
+        if self.basis is not None:
+            self.old = os.environ.get("MPG_BASIS")
+            os.environ["MPG_BASIS"] = self.basis
+
+    def __exit__(self, *exc):
+        if self.basis is not None:
+            if self.old is None:
+                os.environ.pop("MPG_BASIS", None)
+            else:
+                os.environ["MPG_BASIS"] = self.old
+        return False
 
 
 def run_solve(fn, args: SolveArgs, n: int, cycle_cap: int = 4096, step_cap: int = 1 << 17) -> Result:
@@ -598,7 +634,8 @@ def run_solve(fn, args: SolveArgs, n: int, cycle_cap: int = 4096, step_cap: int 
     r.x_out = dp(x)
     r.cycle_cap, r.cyc_r_norm, r.cyc_normalization, r.cyc_beta = cycle_cap, dp(cr), dp(cn), dp(cb)
     r.step_cap, r.step_res, r.step_cycle = step_cap, dp(sr), sc.ctypes.data_as(C.POINTER(C.c_int32))
-    st = fn(C.byref(args), C.byref(r))
+    with _basis_setting(args):
+        st = fn(C.byref(args), C.byref(r))
     msg = r.message.decode(errors="replace")
     if st != 0:
         raise RuntimeError(f"solve failed ({st}): {msg}")
@@ -827,6 +864,16 @@ def solve_multi_gpu(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, 
     return res
 
 
+class _Layout(dict):
+    """Engine.spmv_layout()'s dict: entries of optional features are listed
+    only where they are on; "basis" reads "f32" where it is not listed."""
+
+    def __missing__(self, key):
+        if key == "basis":
+            return "f32"
+        raise KeyError(key)
+
+
 class Engine:
     """Stepped fused engine (mpg_engine_*): set up once, then advance the
     restarted solve cycle by cycle — what bench.py times. Engine.distributed
@@ -840,18 +887,19 @@ class Engine:
         self._lib = host_lib()
         self._h = C.c_void_p()
         err = C.create_string_buffer(512)
-        if _dist is None:
-            st = self._lib.mpg_engine_create(C.byref(self._args), C.byref(self._h), err, 512)
-        else:
-            plan, link, nranks, rank = _dist
-            self._plan = plan
-            if isinstance(link, (bytes, bytearray)):
-                st = self._lib.mpg_engine_create_dist(C.byref(self._args), plan._h, link, nranks, rank,
-                                                      C.byref(self._h), err, 512)
+        with _basis_setting(self._args):
+            if _dist is None:
+                st = self._lib.mpg_engine_create(C.byref(self._args), C.byref(self._h), err, 512)
             else:
-                self._transport = link  # keeps the callbacks alive
-                st = self._lib.mpg_engine_create_dist_host(C.byref(self._args), plan._h, C.byref(link.c), nranks,
-                                                           rank, C.byref(self._h), err, 512)
+                plan, link, nranks, rank = _dist
+                self._plan = plan
+                if isinstance(link, (bytes, bytearray)):
+                    st = self._lib.mpg_engine_create_dist(C.byref(self._args), plan._h, link, nranks, rank,
+                                                          C.byref(self._h), err, 512)
+                else:
+                    self._transport = link  # keeps the callbacks alive
+                    st = self._lib.mpg_engine_create_dist_host(C.byref(self._args), plan._h, C.byref(link.c), nranks,
+                                                               rank, C.byref(self._h), err, 512)
         if st:
             raise RuntimeError(f"mpg_engine_create: {err.value.decode()}")
 
@@ -977,7 +1025,10 @@ class Engine:
         for (mpg_engine_prec_interval). With prec="gmres_poly" it reports
         "prec_sweeps", the number of roots, and "prec_roots": the roots as a
         list of complex numbers in the order they are applied
-        (mpg_engine_prec_roots)."""
+        (mpg_engine_prec_roots). "basis" (mpg_engine_basis) is "f16" or
+        "f16emu" under a compressed or emulated Krylov basis; like the other
+        optional entries it is not listed for the default, where looking it
+        up gives "f32"."""
         f, w, cb, st, win = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         if self._lib.mpg_engine_spmv_layout(self._h, C.byref(f), C.byref(w), C.byref(cb), C.byref(st), C.byref(win)):
             raise RuntimeError("mpg_engine_spmv_layout failed")
@@ -991,18 +1042,20 @@ class Engine:
         stream = int(self._lib.mpg_engine_cgs_stream_steps(self._h))
         rider = int(self._lib.mpg_engine_givens_rider(self._h)) == 1
         tail = int(self._lib.mpg_engine_tail_fold(self._h)) == 1
-        return {**({"dots_fused": fused} if fused > 0 else {}), **({"givens_rider": True} if rider else {}),
+        basis = int(self._lib.mpg_engine_basis(self._h))
+        return _Layout({**({"dots_fused": fused} if fused > 0 else {}), **({"givens_rider": True} if rider else {}),
                 **({"tail_fold": True} if tail else {}),
                 **({"cgs_stream": stream} if stream > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
                 "stored": st.value, "window": bool(win.value),
                 "slices_per_wave": int(self._lib.mpg_engine_slices_per_wave(self._h)),
                 "givens_folded": bool(self._lib.mpg_engine_givens_folded(self._h) == 1),
                 "accum": {0: "f64", 1: "f32"}[int(self._lib.mpg_engine_accum(self._h))],
+                **({"basis": {1: "f16", 2: "f16emu"}[basis]} if basis else {}),
                 **({"prec_fused": pf} if pf >= 0 else {}),
                 **({"prec_sweeps": ps} if ps >= 0 else {}),
                 **({"prec_interval": (ia.value, ib.value)} if has_iv else {}),
                 **({"prec_roots": [complex(rre[i], rim[i]) for i in range(nroots)]} if nroots >= 0 else {}),
-                "prologue": {1: "csr", 2: "sell", 3: "node"}[int(self._lib.mpg_engine_prologue_format(self._h))]}
+                "prologue": {1: "csr", 2: "sell", 3: "node"}[int(self._lib.mpg_engine_prologue_format(self._h))]})
 
     def step_dots_status(self, k: int) -> int:
         """Status mpg_arnoldi_step_dots's support check gives at step k (0:

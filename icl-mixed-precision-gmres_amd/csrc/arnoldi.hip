@@ -66,7 +66,8 @@ int arnoldi_sell_build(mpg_arnoldi* a, int format) {
         node_prologue_build(a);
         return MPG_OK;
     }
-    if (int st = sell_build(a->ctx, a->d.A, a->d.inner_val, a->d.val_inner, format, a->sell)) return st;
+    // (4: auto's choice among the SELL copy and CSR row blocks, no node blocks)
+    if (int st = sell_build(a->ctx, a->d.A, a->d.inner_val, a->d.val_inner, format == 4 ? 0 : format, a->sell)) return st;
     const char* ne = std::getenv("MPG_NODE");
     if (format == 0 && !(ne && *ne == '0')) {
         const int64_t vb = a->d.inner_val == MPG_F64 ? 8 : a->d.inner_val == MPG_F32 ? 4 : 2;
@@ -169,7 +170,7 @@ int mpg_arnoldi_create(mpg_ctx_t ctx, const mpg_arnoldi_desc* desc, mpg_arnoldi_
         return MPG_ERR_ALLOC;
     }
     a->last_part = a->partial;
-    if (desc->spmv_format < 0 || desc->spmv_format > 3) {
+    if (desc->spmv_format < 0 || desc->spmv_format > 4) {
         mpg_arnoldi_destroy(a);
         return MPG_ERR_ARG;
     }
@@ -434,6 +435,41 @@ int mpg_arnoldi_set_accum(mpg_arnoldi_t a, int accum) {
 }
 
 int mpg_arnoldi_accum(mpg_arnoldi_t a) { return !a ? MPG_ERR_ARG : a->acc32 ? MPG_ACCUM_F32 : MPG_ACCUM_F64; }
+
+int mpg_arnoldi_set_basis(mpg_arnoldi_t a, int basis) {
+    if (!a || (basis != MPG_BASIS_F32 && basis != MPG_BASIS_F16 && basis != MPG_BASIS_F16EMU)) return MPG_ERR_ARG;
+    if (basis == a->basis) return MPG_OK;
+    // set once: a workspace that took another storage keeps it (its CGS update form went with it)
+    if (a->basis != MPG_BASIS_F32) return MPG_ERR_ARG;
+    if (basis != MPG_BASIS_F32) {
+        // built for mode mixed (fp32 Arnoldi and values, fp64 residual) on CSR
+        // row blocks and, compressed, on the SELL copy; not on node blocks
+        if (a->combo != 3 || a->node.nblk > 0) return MPG_ERR_UNSUPPORTED;
+        if (basis == MPG_BASIS_F16EMU && a->sell.nslices > 0) return MPG_ERR_UNSUPPORTED;
+    }
+    // V again in the new element size: 2 bytes and ld a multiple of 128
+    // entries (256 B), or T's layout
+    const size_t esize = basis == MPG_BASIS_F16 ? 2 : a->tsize;
+    const int64_t align = 256 / (int64_t)esize;
+    int64_t ld = ((int64_t)a->d.n + align - 1) / align * align;
+    if (ld == 0) ld = align;
+    (void)hipStreamSynchronize(a->ctx->stream);
+    void* V = nullptr;
+    const size_t bytes = (size_t)ld * (a->d.m + 1) * esize;
+    if (hipMalloc(&V, bytes) != hipSuccess) return MPG_ERR_ALLOC;
+    if (hipMemsetAsync(V, 0, bytes, a->ctx->stream) != hipSuccess) {
+        (void)hipFree(V);
+        return MPG_ERR_ALLOC;
+    }
+    if (a->V) (void)hipFree(a->V);
+    a->V = V;
+    a->ld = ld;
+    a->basis = basis;
+    if (basis != MPG_BASIS_F32) a->cgs_pref = 0;  // the plain CGS update
+    return MPG_OK;
+}
+
+int mpg_arnoldi_basis(mpg_arnoldi_t a) { return !a ? MPG_ERR_ARG : a->basis; }
 
 int mpg_arnoldi_prologue_format(mpg_arnoldi_t a) {
     if (!a) return MPG_ERR_ARG;

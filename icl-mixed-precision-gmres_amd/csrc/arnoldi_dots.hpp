@@ -63,22 +63,29 @@ __global__ __launch_bounds__(BS) void k_panel_dots(int n, const T* __restrict__ 
 // SpMV phase of the same launch left them, and may hold the lane's first
 // batch of earlier columns, loaded ahead of that phase (kHeld > 0: columns
 // 0..kHeld-1 of the lane's first row group, in held[]).
-template <class T, class A>
+// BT: the basis' storage (basis.hpp): V is read as stored, 4 rows per load
+// (8 bytes of a compressed basis, twice the columns per batch), and used as
+// Basis<T, BT>::Raw4::at gives it: the same products in the same order.
+template <class T, class A, class BT = T>
 struct DotsGlobal {
     static constexpr bool kStaged = false;
     static constexpr int kHeld = 0;
+    using R4 = typename Basis<T, BT>::Raw4;
     const T* __restrict__ w;
-    Raw4<T> held[1];
+    R4 held[1];
     __device__ __forceinline__ void load_w(int i, A (&wv)[4]) const { Row4<T>::load(w + i, wv); }
-    __device__ __forceinline__ Raw4<T> newest(int) const { return Raw4<T>(); }
+    __device__ __forceinline__ R4 newest(int) const { return R4(); }
 };
 
-template <class T, int BS, int NC, class A = double, class SRC>
-__device__ __forceinline__ void dots_panel_from(int n, const T* __restrict__ V, int64_t ld, const SRC& src,
-                                           double* __restrict__ partial, unsigned G = gridDim.x) {
+template <class T, int BS, int NC, class A = double, class BT = T, class SRC>
+__device__ __forceinline__ void dots_panel_from(int n, const typename Basis<T, BT>::elem* __restrict__ V, int64_t ld,
+                                           const SRC& src, double* __restrict__ partial, unsigned G = gridDim.x) {
     static_assert(NC >= 1 && NC <= kNC, "one panel");
+    using Bs = Basis<T, BT>;
     constexpr int NP = Pow2Ceil<NC>::v;
-    constexpr int B = kColBatch<T>;
+    // (a compressed basis doubles the batch in the fp32 class only: with 32 fp64
+    // accumulators the 16-column batch spilled, 12 B of scratch per lane)
+    constexpr int B = sizeof(A) == 8 ? kColBatch<T> : Bs::kBatch;
     A acc[NP];
 #pragma unroll
     for (int c = 0; c < NP; ++c) acc[c] = A(0);
@@ -89,7 +96,7 @@ __device__ __forceinline__ void dots_panel_from(int n, const T* __restrict__ V, 
         src.load_w(i, wv);
 #pragma unroll
         for (int c0 = 0; c0 < NC; c0 += B) {
-            Raw4<T> v[B];
+            typename Bs::Raw4 v[B];
 #pragma unroll
             for (int u = 0; u < B; ++u)
                 if (c0 + u < NC) {
@@ -115,24 +122,28 @@ __device__ __forceinline__ void dots_panel_from(int n, const T* __restrict__ V, 
         for (int i = n4 + blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
             const A wi = (A)src.w[i];
 #pragma unroll
-            for (int c = 0; c < NC; ++c) acc[c] += (A)V[(int64_t)c * ld + i] * wi;
+            for (int c = 0; c < NC; ++c) acc[c] += Bs::template get<A>(V + (int64_t)c * ld + i) * wi;
         }
     }
     store_partials<NP, BS>(acc, NC, partial, G);
 }
 
-template <class T, int BS, int NC, class A = double>
-__device__ __forceinline__ void dots_panel(int n, const T* __restrict__ V, int64_t ld, const T* __restrict__ w,
-                                           double* __restrict__ partial) {
-    dots_panel_from<T, BS, NC, A>(n, V, ld, DotsGlobal<T, A>{w, {}}, partial);
+template <class T, int BS, int NC, class A = double, class BT = T>
+__device__ __forceinline__ void dots_panel(int n, const typename Basis<T, BT>::elem* __restrict__ V, int64_t ld,
+                                           const T* __restrict__ w, double* __restrict__ partial) {
+    dots_panel_from<T, BS, NC, A, BT>(n, V, ld, DotsGlobal<T, A, BT>{w, {}}, partial);
 }
 
-template <class T, int BS, int NC, bool STAMP = false, class A = double>
+// AT: the accumulation class, or WithBasis<A, B> for a compressed basis
+// (basis.hpp), read as stored through basis_ptr.
+template <class T, int BS, int NC, bool STAMP = false, class AT = double>
 __global__ __launch_bounds__(BS) void k_dots_nc(int n, const T* __restrict__ V, int64_t ld,
                                                 const T* __restrict__ w, double* __restrict__ partial,
                                                 unsigned long long* stamp) {
+    using A = typename AccOf<AT>::type;
+    using Bs = BasisOf<T, AT>;
     stamp_at<STAMP>(stamp, 0);
-    dots_panel<T, BS, NC, A>(n, V, ld, w, partial);
+    dots_panel<T, BS, NC, A, typename AccOf<AT>::template basis<T>>(n, basis_ptr<Bs>(V), ld, w, partial);
     stamp_at<STAMP>(stamp, 1);
 }
 

@@ -80,18 +80,28 @@ int launch_tuple(mpg_ctx* c, K kern, dim3 grid, dim3 block, const std::tuple<X..
 template <class A>
 int spmv_dots_check(const mpg_arnoldi* a, int k) {
     if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
-    if (!std::is_same_v<A, double> || a->d.n <= 0 || a->sell.nslices == 0 || !a->sell.c16 || !a->sell.win ||
+    if (!std::is_same_v<A, double> || a->basis != MPG_BASIS_F32 || a->d.n <= 0 || a->sell.nslices == 0 || !a->sell.c16 || !a->sell.win ||
         (a->combo != 2 && a->combo != 3) || k + 1 > kNC || a->d.orth == kOrthMGS)
         return MPG_ERR_UNSUPPORTED;
     return MPG_OK;
 }
 
+// The kernels with a compressed or emulated basis (mpg_arnoldi_set_basis) are
+// built for an fp32 Arnoldi on fp32 values; set_basis admits no other workspace.
+template <class T, class VI>
+constexpr bool kBasisBuilt = std::is_same_v<T, float> && std::is_same_v<VI, float>;
+inline bool plain_basis(const mpg_arnoldi* a) { return a->basis == MPG_BASIS_F32; }
+inline bool half_basis(const mpg_arnoldi* a) { return a->basis == MPG_BASIS_F16; }
+
 template <class A>
 int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
     if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
+    if (dots && !plain_basis(a)) return MPG_ERR_UNSUPPORTED;  // (the fused dots read an fp32 basis)
     if (dots)
         if (int st = spmv_dots_check<A>(a, k)) return st;
     if (fold && (k < 1 || a->d.m > kFoldMaxM)) return MPG_ERR_ARG;
+    // (no node blocks under set_basis; of the CSR kernel's measurement modes only the default is built)
+    if (!plain_basis(a) && (a->node.nblk > 0 || (a->sell.nslices == 0 && csr_mode() != 0))) return MPG_ERR_UNSUPPORTED;
     const mpg_csr* Acsr = a->d.A;
     int st = dispatch_acc<A>(a->combo, [&](auto t, auto, auto p, auto vi) {
         using T = decltype(t);
@@ -108,6 +118,7 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
                 using CI = decltype(ci);
                 constexpr int Wc = decltype(wc)::value;
                 // the step kernels' arguments (k_step_sell takes a sorted copy's rows behind them)
+                // (a compressed V travels as T*: the kernels view it through basis_ptr)
                 auto args = [&](SellDots dd) {
                     return sell_args<CI, typename SellStore<VI>::type>(
                         a, S,
@@ -145,6 +156,14 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
                         auto pair = [&](auto bec, auto pgc) {
                             return with_flag(fold, [&](auto fo) {
                                 const int grid = (S.nslices + 2 * (kStepSellBlock / kWave) - 1) / (2 * (kStepSellBlock / kWave));
+                                if constexpr (kBasisBuilt<T, VI>) {
+                                    if (half_basis(a))
+                                        return launch_tuple(a->ctx,
+                                                            k_step_sell2<T, P, VI, Wc, WN, decltype(fo)::value, decltype(bec)::value,
+                                                                         kStepSellBlock, decltype(pgc)::value,
+                                                                         WithBasis<A, basis_f16>>,
+                                                            dim3(grid), dim3(kStepSellBlock), args(SellDots{}));
+                                }
                                 return launch_tuple(a->ctx,
                                                     k_step_sell2<T, P, VI, Wc, WN, decltype(fo)::value, decltype(bec)::value,
                                                                  kStepSellBlock, decltype(pgc)::value, A>,
@@ -162,6 +181,13 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
                     auto step = [&](auto pipe) {
                         return with_flag(fold, [&](auto fo) {
                             return with_flag(sell_uniform(S), [&](auto uni) {
+                                if constexpr (kBasisBuilt<T, VI>) {
+                                    if (half_basis(a))
+                                        return launch(k_step_sell<T, P, VI, CI, Wc, WN, decltype(fo)::value, 0, kStepSellBlock,
+                                                                  decltype(uni)::value, decltype(pipe)::value,
+                                                                  WithBasis<A, basis_f16>>,
+                                                      SellDots{}, BSC());
+                                }
                                 return launch(k_step_sell<T, P, VI, CI, Wc, WN, decltype(fo)::value, 0, kStepSellBlock,
                                                           decltype(uni)::value, decltype(pipe)::value, A>,
                                               SellDots{}, BSC());
@@ -194,6 +220,20 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
                 });
             });
         }
+        if constexpr (kBasisBuilt<T, VI>) {
+            if (!plain_basis(a))
+                return with_flag(fold, [&](auto fo) {
+                    return with_flag(half_basis(a), [&](auto hb) {
+                        using BT = std::conditional_t<decltype(hb)::value, basis_f16, basis_f16emu>;
+                        launch_timed(a->ctx, k_step_spmv<T, P, VI, decltype(fo)::value, 0, WithBasis<A, BT>>, dim3(rb_grid(a)),
+                            dim3(kBlock), Acsr->blocks, Acsr->nblocks, Acsr->rowptr, Acsr->col,
+                            static_cast<const VI*>(a->d.val_inner), Acsr->nnz, static_cast<const T*>(a->w[k & 1]),
+                            static_cast<const T*>(a->inv()), static_cast<T*>(a->V), a->ld, k,
+                            diag, static_cast<T*>(a->w[(k + 1) & 1]), gf, a->d.inner_row_exp);
+                        return (int)MPG_OK;
+                    });
+                });
+        }
         return with_int<4>(csr_mode(), [&](auto mode) {
             return with_flag(fold, [&](auto fo) {
                 launch_timed(a->ctx, k_step_spmv<T, P, VI, decltype(fo)::value, decltype(mode)::value, A>, dim3(rb_grid(a)),
@@ -225,7 +265,7 @@ template <class A>
 int step_dots_check(const mpg_arnoldi* a, int k) {
     if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
     const SellCopy& S = a->sell;
-    const bool ok = std::is_same_v<A, float> && (a->combo == 2 || a->combo == 3) &&  // fp32 basis, fp32 values
+    const bool ok = std::is_same_v<A, float> && (a->combo == 2 || a->combo == 3) && plain_basis(a) &&  // fp32 basis, fp32 values
                     a->d.orth != kOrthMGS && a->d.orth != kOrthCGSR && k + 1 <= kNC &&
                     a->d.n > 0 && a->d.n % 4 == 0 &&  // (dots_panel's tail rows belong to workgroup 0's sums)
                     (int64_t)a->Gd * kStepDotsRows >= a->d.n &&  // one pass
@@ -303,11 +343,25 @@ int dots_run(mpg_arnoldi_t a, int k, bool combine) {
     if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
     const int ndots_all = a->d.orth == kOrthMGS ? 1 : k + 1;
     if (combine && ndots_all > kNC) return MPG_ERR_ARG;
+    // a compressed or emulated basis: the one-panel CGS / CGSR dots only
+    if (!plain_basis(a) && (combine || ndots_all > kNC || a->d.orth == kOrthMGS)) return MPG_ERR_UNSUPPORTED;
     // an armed stamp belongs to this launch whatever its form (disarmed
     // here); only the one-panel k_dots_nc stores stamps
     unsigned long long* sp = take_stamp(a, (int64_t)a->Gd * (kCombineBlock / kWave));
-    int st = dispatch_acc<A>(a->combo, [&](auto t, auto, auto, auto) {
+    int st = dispatch_acc<A>(a->combo, [&](auto t, auto, auto, auto vi) {
         using T = decltype(t);
+        if constexpr (kBasisBuilt<T, decltype(vi)>) {
+            if (half_basis(a))
+                return with_nc<kNC>(ndots_all, [&](auto nc) {
+                    return with_flag(sp != nullptr, [&](auto stamped) {
+                        k_dots_nc<T, kCombineBlock, decltype(nc)::value, decltype(stamped)::value, WithBasis<A, basis_f16>>
+                            <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, static_cast<const T*>(a->V),
+                                                                           a->ld, static_cast<const T*>(a->w[(k + 1) & 1]),
+                                                                           a->dpart, sp);
+                        return (int)MPG_OK;
+                    });
+                });
+        }
         if (combine) {
             k_panel_dots<T, kCombineBlock, true, A><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
                 a->d.n, static_cast<const T*>(a->V), a->ld, 0, ndots_all, static_cast<const T*>(a->w[(k + 1) & 1]),
@@ -403,6 +457,7 @@ void cgs_stream_launch(mpg_arnoldi_t a, const float* V, const double* src, int p
 template <class A>
 int cgs_stream_check(const mpg_arnoldi* a, int k) {
     if (!a || k < 0 || k >= a->d.m) return MPG_ERR_ARG;
+    if (!plain_basis(a)) return MPG_ERR_UNSUPPORTED;  // (the ring streams an fp32 basis)
     if (k + 1 > kNC || a->d.orth == kOrthCGSR) return 0;
     int form = kCgsPlain;
     dispatch_acc<A>(a->combo, [&](auto t, auto, auto, auto) {
@@ -420,6 +475,10 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
     if (!a || k < 0 || k >= a->d.m || pass < 0 || pass > 1 || k + 1 > 256) return MPG_ERR_ARG;
     const bool cgsr = a->d.orth == kOrthCGSR;
     const bool next_dots = cgsr && pass == 0 && !no_next;
+    // a compressed or emulated basis: the one-panel plain forms only (CGSR's
+    // first pass from the sums, the last pass from the sums or the partials)
+    if (!plain_basis(a) && (givens || no_next || k + 1 > kNC || (next_dots && from_partials) || a->d.orth == kOrthMGS))
+        return MPG_ERR_UNSUPPORTED;
     if (givens && (next_dots || a->d.m > kFoldMaxM || from_partials)) return MPG_ERR_ARG;
     if (no_next && (!cgsr || !from_partials || k + 1 <= kNC)) return MPG_ERR_ARG;
     // from_partials: the coefficients are summed from the preceding one-panel
@@ -432,11 +491,37 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
     // an armed stamp belongs to this launch whatever its form (disarmed here);
     // only the one-panel product form below stores stamps
     unsigned long long* sp = take_stamp(a, (int64_t)a->Gd * (kCombineBlock / kWave));
-    int st = dispatch_acc<A>(a->combo, [&](auto t, auto, auto, auto) {
+    int st = dispatch_acc<A>(a->combo, [&](auto t, auto, auto, auto vi) {
         using T = decltype(t);
         T* coef_out = pass == 0 ? static_cast<T*>(a->H) + (int64_t)k * (a->d.m + 1) : static_cast<T*>(a->corr());
         T* w = static_cast<T*>(a->w[(k + 1) & 1]);
         const GivensArgs<T> g = givens_args<T>(a, k);
+        if constexpr (kBasisBuilt<T, decltype(vi)>) {
+            if (half_basis(a)) {
+                using AB = WithBasis<A, basis_f16>;
+                const T* Vh = static_cast<const T*>(a->V);  // (viewed as fp16 through basis_ptr)
+                if (!from_partials) sp = nullptr;
+                return with_nc<kNC>(k + 1, [&](auto nc) {
+                    constexpr int NC = decltype(nc)::value;
+                    if (next_dots)  // (256-thread workgroups, as the fp32 basis' form)
+                        k_cgs_update_nc<T, kBlock, NC, false, true, false, false, AB>
+                            <<<row_grid(a), kBlock, 0, a->ctx->stream>>>(a->d.n, Vh, a->ld, src, 0, coef_out, w, a->partial,
+                                                                          nullptr);
+                    else if (from_partials)
+                        return with_flag(sp != nullptr, [&](auto stamped) {
+                            k_cgs_update_nc<T, kCombineBlock, NC, true, false, false, decltype(stamped)::value, AB>
+                                <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, Vh, a->ld, src, part_G, coef_out, w,
+                                                                               a->partial, sp);
+                            return (int)MPG_OK;
+                        });
+                    else
+                        k_cgs_update_nc<T, kCombineBlock, NC, false, false, false, false, AB>
+                            <<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(a->d.n, Vh, a->ld, src, 0, coef_out, w, a->partial,
+                                                                           nullptr);
+                    return (int)MPG_OK;
+                });
+            }
+        }
         if (next_dots && k + 1 <= kNC && !from_partials) {
             // 256-thread workgroups (the NC fp64 dot accumulators need more
             // than the 128 VGPRs of a 1024-thread one) -> row_grid partials
@@ -521,6 +606,7 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
 template <class A>
 int mgs_run(mpg_arnoldi_t a, int k, int j, bool from_partials) {
     if (!a || k < 0 || k >= a->d.m || j < 0 || j > k) return MPG_ERR_ARG;
+    if (!plain_basis(a)) return MPG_ERR_UNSUPPORTED;
     // from_partials: h_jk from the previous launch's partials; the update
     // writes into the other partial buffer (the previous one is still read)
     const double* src = from_partials ? a->last_part : a->sums;
@@ -560,9 +646,19 @@ template <class A>
 int update_run(mpg_arnoldi_t a, int k) {
     if (!a || k < 0 || k > a->d.m || k > 1024) return MPG_ERR_ARG;
     if (k == 0) return MPG_OK;
-    int st = dispatch_acc<A>(a->combo, [&](auto t, auto x, auto, auto) {
+    if (!plain_basis(a) && k > kNC) return MPG_ERR_UNSUPPORTED;  // one panel
+    int st = dispatch_acc<A>(a->combo, [&](auto t, auto x, auto, auto vi) {
         using T = decltype(t);
         using X = decltype(x);
+        if constexpr (kBasisBuilt<T, decltype(vi)> && std::is_same_v<X, double>) {
+            if (half_basis(a))
+                return with_nc<kNC>(k, [&](auto nc) {
+                    k_update_x_nc<T, X, decltype(nc)::value, WithBasis<A, basis_f16>><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
+                        a->d.n, static_cast<const T*>(a->V), a->ld, static_cast<const T*>(a->s()),
+                        static_cast<const T*>(a->H), a->d.m + 1, static_cast<X*>(a->d.x));
+                    return (int)MPG_OK;
+                });
+        }
         if (k <= kNC) {  // x is an aligned allocation: row groups of 4 are 16/32-B aligned
             return with_nc<kNC>(k, [&](auto nc) {
                 k_update_x_nc<T, X, decltype(nc)::value, A><<<a->Gd, kCombineBlock, 0, a->ctx->stream>>>(
@@ -599,7 +695,7 @@ int update_run(mpg_arnoldi_t a, int k) {
 // fold_parts_sum adds in k_givens' order). Asked without launching:
 // update_tail_ok.
 inline bool update_tail_ok(const mpg_arnoldi* a) {
-    return a && a->d.m >= 1 && a->d.m <= kNC && a->Gd <= kBlock;
+    return a && a->d.m >= 1 && a->d.m <= kNC && a->Gd <= kBlock && plain_basis(a);
 }
 
 template <class A>

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "arnoldi_givens.hpp"
+#include "basis.hpp"
 #include "lds_ring.hpp"
 #include "panel.hpp"
 
@@ -31,12 +32,19 @@ namespace {
 // The partials are loaded outside the compiler's wait bookkeeping (it would
 // wait vmcnt(0) at their first use and drain the ring). Same operands, the
 // columns added in the same ascending order.
+// AT: the accumulation class, or WithBasis<A, B> for a compressed basis
+// (basis.hpp), which takes the plain forms only (no PF, no STREAM: both hold
+// or stream an fp32 basis), its columns read as stored, 4 rows per 8-byte
+// load, twice the columns per batch.
 template <class T, int BS, int NC, bool FROM_PARTS = false, bool NEXT_DOTS = false, bool PF = false,
-          bool STAMP = false, class A = double, bool STREAM = false>
-__global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict__ V, int64_t ld,
+          bool STAMP = false, class AT = double, bool STREAM = false>
+__global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict__ V_, int64_t ld,
                                                       const double* __restrict__ sums, int part_G,
                                                       T* __restrict__ coef_out, T* __restrict__ w,
                                                       double* __restrict__ partial, unsigned long long* stamp) {
+    using A = typename AccOf<AT>::type;
+    using Bs = BasisOf<T, AT>;
+    const typename Bs::elem* __restrict__ V = basis_ptr<Bs>(V_);
     static_assert(NC >= 1 && NC <= kNC, "one panel");
     stamp_at<STAMP>(stamp, 0);
     static_assert(!FROM_PARTS || BS >= 32 * NC, "32 lanes per column");
@@ -44,13 +52,15 @@ __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict
     static_assert(!PF || NC <= kColBatch<T>, "the prefetch form holds one batch of columns (the only form run)");
     static_assert(!STREAM || (FROM_PARTS && !NEXT_DOTS && !PF && !STAMP && sizeof(T) == 4 && sizeof(A) == 4),
                   "the streaming form: the last pass with in-launch sums, fp32 basis, fp32 class");
-    constexpr int B = kColBatch<T>;
+    static_assert(std::is_same_v<AT, A> || (!PF && !STREAM), "fp32 basis only");
+    constexpr int B = Bs::kBatch;
     constexpr int B0 = NC < B ? NC : B;
     constexpr int R = NC < kStreamSlots ? NC : kStreamSlots;  // the ring's depth
     __shared__ A coef[NC];
     const int n4 = n & ~3;
     const int i_first = 4 * (blockIdx.x * BS + threadIdx.x);
-    Raw4<T> pw, pv[PF ? B0 : 1];
+    Raw4<T> pw;
+    typename Bs::Raw4 pv[PF ? B0 : 1];
     // clamped row of the early requests: every lane reads valid memory
     const int ip = i_first < n4 ? i_first : 0;
     unsigned ring_lane = 0;  // LDS byte address of this lane's 16 bytes of slot 0
@@ -176,7 +186,7 @@ __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict
         A t[4] = {A(0), A(0), A(0), A(0)};
 #pragma unroll
         for (int c0 = 0; c0 < NC; c0 += B) {
-            Raw4<T> v[B];
+            typename Bs::Raw4 v[B];
 #pragma unroll
             for (int u = 0; u < B; ++u)
                 if (c0 + u < NC) {
@@ -198,7 +208,7 @@ __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict
         if constexpr (NEXT_DOTS) {
 #pragma unroll
             for (int c0 = 0; c0 < NC; c0 += B) {
-                Raw4<T> v[B];
+                typename Bs::Raw4 v[B];
 #pragma unroll
                 for (int u = 0; u < B; ++u)
                     if (c0 + u < NC) v[u].load(V + (int64_t)(c0 + u) * ld + i);
@@ -214,12 +224,12 @@ __global__ __launch_bounds__(BS) void k_cgs_update_nc(int n, const T* __restrict
     for (int i = n4 + blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
         A t = A(0);
 #pragma unroll
-        for (int j = 0; j < NC; ++j) t += (A)V[(int64_t)j * ld + i] * coef[j];
+        for (int j = 0; j < NC; ++j) t += Bs::template get<A>(V + (int64_t)j * ld + i) * coef[j];
         const T wi = T(-1) * (T)t + T(1) * w[i];
         w[i] = wi;
         if constexpr (NEXT_DOTS) {
 #pragma unroll
-            for (int c = 0; c < NC; ++c) acc[c] += (A)V[(int64_t)c * ld + i] * (A)wi;
+            for (int c = 0; c < NC; ++c) acc[c] += Bs::template get<A>(V + (int64_t)c * ld + i) * (A)wi;
         } else {
             acc[0] += (A)wi * (A)wi;
         }

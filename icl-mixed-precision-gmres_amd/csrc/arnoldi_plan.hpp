@@ -138,6 +138,10 @@ struct mpg_arnoldi {
     // fp32 Arnoldi with fp32 accumulation (mpg_arnoldi_set_accum): the
     // launches go through arnoldi_acc32.hip's A = float instantiations
     bool acc32 = false;
+    // the basis' storage (mpg_arnoldi_set_basis; basis.hpp): MPG_BASIS_F32,
+    // _F16 (V holds fp16_rne(2^14 v), ld a multiple of 128 entries) or _F16EMU
+    // (the same values as fp32). Other than F32: the plain launch forms only.
+    int basis = 0;
     // the cycle's tail in one launch (k_update_tail_nc): where it keeps the x
     // it read (mpg_arnoldi_set_x_snapshot), and whether its rotated column
     // H(:, m-1) still waits in tail_stage() for the finish launch

@@ -6,6 +6,7 @@
 
 #include "arnoldi_prologue.hpp"
 #include "arnoldi_givens.hpp"
+#include "basis.hpp"
 #include "handoff.hpp"
 
 namespace {
@@ -16,7 +17,10 @@ namespace {
 // that Givens step folded in (fold.norm2 != nullptr). The Gram-Schmidt dots
 // follow in k_panel_dots (measured: dots inside this gather-bound launch
 // cost more than the separate pass, 71 us vs 30 + 20 us on BAND-10M).
-template <class T, class P, class VI, bool FOLD, int MODE = 0, class A = double>
+// AT: the accumulation class, or WithBasis<A, B> for a compressed or emulated
+// basis (basis.hpp): the operator is then applied to the stored value
+// round(T(w_prev * inv)), which is also what V(:,k) receives.
+template <class T, class P, class VI, bool FOLD, int MODE = 0, class AT = double>
 __global__ __launch_bounds__(kBlock) void k_step_spmv(const int32_t* __restrict__ blocks, int nblocks,
                                                       const int32_t* __restrict__ rowptr,
                                                       const int32_t* __restrict__ col, const VI* __restrict__ val,
@@ -24,10 +28,12 @@ __global__ __launch_bounds__(kBlock) void k_step_spmv(const int32_t* __restrict_
                                                       const T* __restrict__ inv_p, T* __restrict__ V, int64_t ld,
                                                       int k, const P* __restrict__ diag, T* __restrict__ w,
                                                       GivensFold<T> fold, const int8_t* __restrict__ rexp) {
+    using A = typename AccOf<AT>::type;
+    using Bs = BasisOf<T, AT>;
     __shared__ double prod[kNnzCap];
     __shared__ double scratch[kBlock / kWave];
     const T inv = fold_givens<FOLD, T, A>(fold, inv_p);
-    T* __restrict__ Vk = V + (int64_t)k * ld;
+    typename Bs::elem* __restrict__ Vk = basis_ptr<Bs>(V) + (int64_t)k * ld;
     struct Ops {
         T wp;
         P d;
@@ -37,14 +43,15 @@ __global__ __launch_bounds__(kBlock) void k_step_spmv(const int32_t* __restrict_
     // bit 2 (measurement only, wrong results): no gathers, x = 1
     for_rows<(MODE & 1) != 0, (MODE & 2) != 0, A>(
         blocks, nblocks, rowptr, col, val, nnz,
-        [&](int c) { return (MODE & 4) ? 1.0 + 0.0 * c : (double)(T)(wprev[c] * inv); },
+        [&](int c) { return (MODE & 4) ? 1.0 + 0.0 * c : (double)Bs::round((T)(wprev[c] * inv)); },
         [&](int i) { return Ops{wprev[i], diag ? diag[i] : P(0), rexp ? (int)rexp[i] : 0}; },
         [&](int i, double sum, const Ops& o) {
             const T t = (T)ldexp(sum, -o.e);  // spmv(1, A, v, 0, w): y = 1*t (exact unscale)
             P pw = (P)t;         // = precond<T, P> with the diagonal loaded ahead
             if (diag) pw = P(0) * pw + P(1) * o.d * pw;
             w[i] = (T)pw;
-            Vk[i] = o.wp * inv;
+            const T vk = Bs::round(o.wp * inv);
+            Bs::store(&Vk[i], vk);
         },
         prod, scratch);
 }
@@ -253,8 +260,10 @@ struct SellDots {
     double* out;       // [c * ng + g]
 };
 
+// AT: the accumulation class, or WithBasis<A, B> for a compressed basis
+// (basis.hpp; no fused dots): v_k is rounded wherever it is formed.
 template <class T, class P, class VI, class CI, int W, bool WIN, bool FOLD, int DN = 0, int BS = kBlock,
-          bool UNI = false, bool PIPE = false, class A = double>
+          bool UNI = false, bool PIPE = false, class AT = double>
 __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, int nslices, const int64_t* __restrict__ off,
                                                       const CI* __restrict__ col,
                                                       const typename SellStore<VI>::type* __restrict__ val,
@@ -269,8 +278,11 @@ __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, in
                                                       const typename SellStore<VI>::type* __restrict__ xval,
                                                       const int8_t* __restrict__ rexp, int64_t ustride, int xcd,
                                                       const int32_t* __restrict__ rows) {
+    using A = typename AccOf<AT>::type;
+    using Bs = BasisOf<T, AT>;
     static_assert(DN == 0 || BS == kBlock, "the fused dots' partials assume kBlock-thread workgroups");
     static_assert(DN == 0 || std::is_same_v<A, double>, "the fused dots accumulate in fp64");
+    static_assert(DN == 0 || std::is_same_v<AT, A>, "the fused dots read an uncompressed basis");
     using S = typename SellStore<VI>::type;
     constexpr int NQ = kWinLen / kWave;
     __shared__ T win[WIN ? BS / kWave : 1][WIN ? kWinLen : 1];
@@ -382,7 +394,7 @@ __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, in
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const int c = row0 - kWinLo + q * kWave + lane;
-                win[wid][q * kWave + lane] = (c >= n_lo && c < n_ext) ? (T)(wr[q] * inv) : T(0);
+                win[wid][q * kWave + lane] = (c >= n_lo && c < n_ext) ? Bs::round((T)(wr[q] * inv)) : T(0);
             }
             wave_lds_sync();
             auto xv = [&](int c) { return (double)win[wid][c - row0 + kWinLo]; };
@@ -393,7 +405,7 @@ __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, in
             }
             vk = win[wid][lane + kWinLo];
         } else {
-            auto xv = [&](int c) { return (double)(T)(wprev[c] * inv); };
+            auto xv = [&](int c) { return (double)Bs::round((T)(wprev[c] * inv)); };
             if (SellCol<CI>::stepped && row.exc) {
                 sum = csr_row_sum<A>(i < n ? row.xrow : -1, xrp, xcol, xval, xv);
             } else if constexpr (PIPE) {
@@ -407,7 +419,7 @@ __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, in
                 Row rb;
                 rb.geom_from(row);
                 auto xraw = [&](int c) { return wprev[c]; };
-                auto xs = [&](T r) { return (double)(T)(r * inv); };
+                auto xs = [&](T r) { return (double)Bs::round((T)(r * inv)); };
                 T x[Row::U][W];
                 for (int q = 0;;) {
                     row.gather(xraw, x);
@@ -432,7 +444,7 @@ __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, in
                     row.sum(q, xv, sum);
                 }
             }
-            vk = (T)(wr[0] * inv);
+            vk = Bs::round((T)(wr[0] * inv));
         }
     }
     T wi = T(0);
@@ -441,7 +453,7 @@ __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, in
         const T t = (T)sum;  // spmv(1, A, v, 0, w): y = 1*t
         wi = precond<T, P>(t, diag, i);
         w[i] = wi;
-        V[(int64_t)k * ld + i] = vk;
+        Bs::store(basis_ptr<Bs>(V) + (int64_t)k * ld + i, vk);
     }
     if constexpr (DN > 0) {
         // the earlier basis columns at this row: clamped, branch-free loads
@@ -485,8 +497,9 @@ __global__ __launch_bounds__(BS) void k_step_sell(int n, int n_lo, int n_ext, in
 // the window). Past the Infinity Cache a slice's loads alone do not keep
 // enough bytes in flight per CU (MI355X_MICROARCH.md: ~72 KiB per CU hides
 // an HBM miss). Same sums in the same order as k_step_sell: same bits.
+// AT: as k_step_sell's.
 template <class T, class P, class VI, int W, bool WIN, bool FOLD, int BE, int BS = kBlock, bool PG = true,
-          class A = double>
+          class AT = double>
 __global__ __launch_bounds__(BS) void k_step_sell2(int n, int n_lo, int n_ext, int nslices, const int64_t* __restrict__ off,
                                                    const int16_t* __restrict__ col,
                                                    const typename SellStore<VI>::type* __restrict__ val,
@@ -500,6 +513,8 @@ __global__ __launch_bounds__(BS) void k_step_sell2(int n, int n_lo, int n_ext, i
                                                    const int32_t* __restrict__ xcol,
                                                    const typename SellStore<VI>::type* __restrict__ xval,
                                                    const int8_t* __restrict__ rexp, int64_t ustride, int xcd) {
+    using A = typename AccOf<AT>::type;
+    using Bs = BasisOf<T, AT>;
     using S = typename SellStore<VI>::type;
     using CI = int16_t;
     constexpr bool UNI = true;
@@ -630,7 +645,7 @@ __global__ __launch_bounds__(BS) void k_step_sell2(int n, int n_lo, int n_ext, i
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const int c = row0 - kWinLo + q * kWave + lane;
-                win[wid][q * kWave + lane] = (c >= n_lo && c < n_ext) ? (T)(wr[q] * inv) : T(0);
+                win[wid][q * kWave + lane] = (c >= n_lo && c < n_ext) ? Bs::round((T)(wr[q] * inv)) : T(0);
             }
             wave_lds_sync();
             auto xv = [&](int c) { return (double)win[wid][c - row0 + kWinLo]; };
@@ -645,21 +660,21 @@ __global__ __launch_bounds__(BS) void k_step_sell2(int n, int n_lo, int n_ext, i
                 vk[p] = win[wid][p * kWave + lane + kWinLo];
             }
         } else {
-            auto xv = [&](int c) { return (double)(T)(wprev[c] * inv); };
+            auto xv = [&](int c) { return (double)Bs::round((T)(wprev[c] * inv)); };
 #pragma unroll
             for (int p = 0; p < SPW; ++p) {
                 const int i = row0 + p * kWave + lane;
                 if (SellCol<CI>::stepped && row[p].exc) {
                     sum[p] = csr_row_sum<A>(live_p[p] && i < n ? row[p].xrow : -1, xrp, xcol, xval, xv);
                 } else {
-                    if constexpr (PRE) row[p].sum_gathered(0, xr[p], [&](T r) { return (double)(T)(r * inv); }, sum[p]);
+                    if constexpr (PRE) row[p].sum_gathered(0, xr[p], [&](T r) { return (double)Bs::round((T)(r * inv)); }, sum[p]);
                     else row[p].sum(0, xv, sum[p]);
                     for (int q = row[p].U; q < row[p].steps; q += row[p].U) {
                         row[p].load(q);
                         row[p].sum(q, xv, sum[p]);
                     }
                 }
-                vk[p] = (T)(wr[p] * inv);
+                vk[p] = Bs::round((T)(wr[p] * inv));
             }
         }
     }
@@ -671,7 +686,7 @@ __global__ __launch_bounds__(BS) void k_step_sell2(int n, int n_lo, int n_ext, i
             if constexpr (std::is_same_v<VI, half_v>) sp = ldexp(sp, -rex[p]);
             const T t = (T)sp;
             w[i] = precond<T, P>(t, diag, i);
-            V[(int64_t)k * ld + i] = vk[p];
+            Bs::store(basis_ptr<Bs>(V) + (int64_t)k * ld + i, vk[p]);
         }
     }
     if constexpr (FOLD) {

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "arnoldi_givens.hpp"
+#include "basis.hpp"
 #include "lds_ring.hpp"
 #include "panel.hpp"
 
@@ -144,12 +145,17 @@ __global__ __launch_bounds__(kBlock) void k_update_x(int n, const T* __restrict_
 // constant: each lane owns 4 rows and loads the basis in batches (the
 // runtime-k form waited for every few columns in turn). Same arithmetic:
 // t = sum_j V_ij y_j in fp64 in j order, x_i = x_i + X(T(t)).
-template <class T, class X, int NC, class A = double>
-__global__ __launch_bounds__(kCombineBlock) void k_update_x_nc(int n, const T* __restrict__ V, int64_t ld,
+// AT: the accumulation class, or WithBasis<A, B> for a compressed basis
+// (basis.hpp), read as stored.
+template <class T, class X, int NC, class AT = double>
+__global__ __launch_bounds__(kCombineBlock) void k_update_x_nc(int n, const T* __restrict__ V_, int64_t ld,
                                                                 const T* __restrict__ y, const T* __restrict__ H,
                                                                 int ldh, X* __restrict__ x) {
     static_assert(NC >= 1 && NC <= kNC, "one panel");
-    constexpr int BS = kCombineBlock, B = kColBatch<T>;
+    using A = typename AccOf<AT>::type;
+    using Bs = BasisOf<T, AT>;
+    const typename Bs::elem* __restrict__ V = basis_ptr<Bs>(V_);
+    constexpr int BS = kCombineBlock, B = Bs::kBatch;
     __shared__ T Hs[NC * kWave];
     __shared__ A ys[NC];
     for (int e = threadIdx.x; e < NC * kWave; e += BS) {
@@ -171,7 +177,7 @@ __global__ __launch_bounds__(kCombineBlock) void k_update_x_nc(int n, const T* _
         A t[4] = {A(0), A(0), A(0), A(0)};
 #pragma unroll
         for (int c0 = 0; c0 < NC; c0 += B) {
-            Raw4<T> v[B];
+            typename Bs::Raw4 v[B];
 #pragma unroll
             for (int u = 0; u < B; ++u)
                 if (c0 + u < NC) v[u].load(V + (int64_t)(c0 + u) * ld + i);
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(kCombineBlock) void k_update_x_nc(int n, const T* _
     for (int i = n4 + blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
         A t = A(0);
 #pragma unroll
-        for (int j = 0; j < NC; ++j) t += (A)V[(int64_t)j * ld + i] * ys[j];
+        for (int j = 0; j < NC; ++j) t += Bs::template get<A>(V + (int64_t)j * ld + i) * ys[j];
         x[i] = x[i] + (X)(T)t;
     }
 }

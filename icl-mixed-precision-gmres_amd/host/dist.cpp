@@ -668,6 +668,18 @@ int solve_rank_threads(const mpg_solve_args* a, int32_t P, mpg_solve_result* r, 
     return MPG_OK;
 }
 
+// MPG_BASIS other than f32 (fused_gmres.hpp) is refused before any rank
+// starts, with its own status: a rank's failure is reported as MPG_ERR_ARG
+int refuse_basis(const mpg_solve_args* a, mpg_solve_result* r) {
+    try {
+        check_basis_args(*a, basis_setting(), false, true);
+    } catch (const StatusError& e) {
+        std::snprintf(r->message, sizeof r->message, "%s", e.what());
+        return e.status;
+    }
+    return MPG_OK;
+}
+
 }  // namespace
 }  // namespace mpg
 
@@ -677,6 +689,7 @@ int mpg_solve_loopback_ex(const mpg_solve_args* a, int32_t P, mpg_solve_result* 
     if (!a || !r || P < 1 || a->n < P) return MPG_ERR_ARG;
     r->status = MPG_RESULT_ERROR;
     r->message[0] = 0;
+    if (int st = mpg::refuse_basis(a, r)) return st;
     Hub hub(P);
     const std::vector<int> devices((size_t)P, a->device);
     return solve_rank_threads(
@@ -692,6 +705,7 @@ int mpg_solve_multi_gpu(const mpg_solve_args* a, int32_t ngpus, const int32_t* d
     if (!a || !r || ngpus < 1 || a->n < ngpus) return MPG_ERR_ARG;
     r->status = MPG_RESULT_ERROR;
     r->message[0] = 0;
+    if (int st = mpg::refuse_basis(a, r)) return st;
     int visible = 0;
     if (hipGetDeviceCount(&visible) != hipSuccess) visible = 0;
     std::vector<int> devices((size_t)ngpus);

@@ -93,6 +93,43 @@ constexpr int kStepDotsLo = 1, kStepDotsHi = 32;
 
 }  // namespace
 
+int basis_setting() {
+    const char* e = std::getenv("MPG_BASIS");
+    if (!e || !*e) return MPG_BASIS_F32;
+    const std::string v = e;
+    if (v == "f32") return MPG_BASIS_F32;
+    if (v == "f16") return MPG_BASIS_F16;
+    if (v == "f16emu") return MPG_BASIS_F16EMU;
+    throw StatusError(MPG_ERR_ARG, "MPG_BASIS = " + v + " is not f32, f16 or f16emu");
+}
+
+const char* basis_name(int basis) {
+    return basis == MPG_BASIS_F16 ? "f16" : basis == MPG_BASIS_F16EMU ? "f16emu" : "f32";
+}
+
+void check_basis_args(const mpg_solve_args& a, int basis, bool surface, bool ranks) {
+    if (basis == MPG_BASIS_F32) return;
+    const std::string name = std::string("basis ") + basis_name(basis);
+    auto refuse = [&](const std::string& why) { throw StatusError(MPG_ERR_UNSUPPORTED, name + " " + why); };
+    if (surface)
+        refuse("is not available on the operator-surface engine: the compressed basis lives in the fused engine's "
+               "Arnoldi kernels");
+    if (ranks)
+        refuse("is not available on a row-partitioned solve: the halo carries the raw w_prev, and the receiver's "
+               "rounding giving the owner's bits is untested");
+    if (a.mode != MPG_MODE_MIXED)
+        refuse("runs in mode mixed only (fp32 Arnoldi on fp32 values, fp64 residual)");
+    if (a.orth == MPG_ORTH_MGS)
+        refuse("runs with orth cgs and cgsr only, not orth mgs: the MGS update has no compressed form");
+    if (a.rlen > 32)
+        refuse("needs rlen <= 32 (one panel of basis columns): rlen = " + std::to_string(a.rlen) +
+               " would take the wide launches, which have no compressed form");
+    if (a.orthloss) refuse("is not available with --orthloss: the loss estimate reads the basis as fp32");
+    if (a.spmv_format == 3) refuse("is not available on node-block storage: node blocks are not built for it");
+    if (basis == MPG_BASIS_F16EMU && a.spmv_format == 2)
+        refuse("is built for the CSR row-block SpMV only (it exists for the tests): not SELL storage");
+}
+
 struct FusedEngine::Impl {
     mpg_ctx_t ctx = nullptr;
     mpg_solve_args args{};
@@ -161,6 +198,7 @@ struct FusedEngine::Impl {
     bool poly = false;
     PolyRoots poly_roots{};
     bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || (nm_asked == 1 && !cheb && !poly); }
+    int basis = MPG_BASIS_F32;  // the basis' storage (MPG_BASIS, read at create; mpg_arnoldi_set_basis)
     bool orthloss = false;    // LostOrthogonality: v_{k+1} stored each step, S / u below
     DevMem loss_S, loss_u;    // (m+1) x (m+1) and m+2 of T, zero-filled (IterUtil.hpp:185-191)
 
@@ -257,6 +295,25 @@ void FusedEngine::Impl::resolve_policy() {
     }
     // the first character of a setting; 0: unset or empty
     auto env = [](const char* name) { const char* v = std::getenv(name); return v ? *v : '\0'; };
+    // A compressed or emulated basis takes the plain launches, as under
+    // MPG_STEP_DOTS=0 MPG_CGS_PREFETCH=0 MPG_TAIL_FOLD=0 whatever those say:
+    // the workspace reports none of the fused forms as supported
+    // (mpg_arnoldi_set_basis), so the plan below holds none. Asking for one
+    // of them is an error, not a silent fall-back.
+    const bool plain_only = basis != MPG_BASIS_F32;
+    if (plain_only) {
+        const char* asked = env("MPG_STEP_DOTS") == '2'      ? "MPG_STEP_DOTS=2"
+                            : env("MPG_FUSE_DOTS") == '2'    ? "MPG_FUSE_DOTS=2"
+                            : env("MPG_FUSE_DOTS") == '1'    ? "MPG_FUSE_DOTS=1"
+                            : env("MPG_CGS_PREFETCH") == '1' ? "MPG_CGS_PREFETCH=1"
+                            : env("MPG_TAIL_FOLD") == '1'    ? "MPG_TAIL_FOLD=1"
+                            : env("MPG_COMBINE") == '1'      ? "MPG_COMBINE=1"
+                                                             : nullptr;
+        if (asked)
+            throw StatusError(MPG_ERR_UNSUPPORTED, std::string("basis ") + basis_name(basis) + ": " + asked +
+                                                       " asks for a fused launch form, which reads an fp32 basis; "
+                                                       "the compressed basis runs the plain forms only");
+    }
     P.pipeline = env("MPG_PIPELINE") != '0';  // 0: read each cycle's report before the next launch
     P.graph = env("MPG_NO_GRAPH") != '1' && (!comm || comm->capturable());
     // Givens(k-1) is folded into SpMV(k) by default (MPG_FOLD_GIVENS=0: its
@@ -275,7 +332,8 @@ void FusedEngine::Impl::resolve_policy() {
     // (ranks: the dots' partials are all-reduced in place first, so the
     // update still sums them itself -- no reduce launch per step)
     P.cgs_partials = !P.combine && orth != MPG_ORTH_MGS &&
-                     (orth == MPG_ORTH_CGSR ? env("MPG_CGS_PARTIALS") == '1' : env("MPG_CGS_PARTIALS") != '0');
+                     (orth == MPG_ORTH_CGSR ? env("MPG_CGS_PARTIALS") == '1' && !plain_only  // (the runtime-count kernel)
+                                            : env("MPG_CGS_PARTIALS") != '0');
     // MPG_FUSE_DOTS=1: the panel dots inside the SELL SpMV launch (SellDots)
     // (=2: required -- an error where the storage does not support it; tests)
     const char denv = env("MPG_FUSE_DOTS");
@@ -346,6 +404,8 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     I.m = a.rlen;
     I.orth = a.orth;
     I.nnz = a.nnz;
+    I.basis = basis_setting();
+    check_basis_args(a, I.basis, false, comm != nullptr);
     const bool ilu = a.prec == MPG_PREC_ILU || a.prec == MPG_PREC_ILU_JACOBI;
     if (ilu && comm)
         throw std::invalid_argument("ILU / ILU-Jacobi factor the whole matrix: not available on a row-partitioned solve");
@@ -569,6 +629,9 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     d.b = I.b.p;
     d.x = I.xp;
     d.spmv_format = a.spmv_format;
+    // a compressed basis: auto picks among CSR row blocks and the SELL copy
+    // (no node blocks); the emulated one is built for the CSR kernel
+    if (I.basis != MPG_BASIS_F32 && a.spmv_format == 0) d.spmv_format = I.basis == MPG_BASIS_F16EMU ? 1 : 4;
     d.n_front = n_front;
     {
         const char* benv = std::getenv("MPG_BJACOBI_FUSE");
@@ -584,6 +647,7 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     I.bj_fused_prologue = mpg_arnoldi_prec_fused(I.arn, 1) == 1;
     // fp32 Arnoldi: the reference's fp32 accumulation class on request (arnoldi.h)
     if (a.accum) check(mpg_arnoldi_set_accum(I.arn, MPG_ACCUM_F32), "mpg_arnoldi_set_accum", ctx);
+    if (I.basis != MPG_BASIS_F32) check(mpg_arnoldi_set_basis(I.arn, I.basis), "mpg_arnoldi_set_basis", ctx);
     if (I.nm_steps) {  // ||M^-1 b|| through the launches every application takes (tmp_t still holds T(b))
         if (I.nm_steps >= 2) I.nm_work0 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
         if (I.nm_steps >= 3) I.nm_work1 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
@@ -1018,6 +1082,7 @@ double FusedEngine::phase_bytes(int which) const {
     const Impl& I = *p_;
     const double n = I.n, z = (double)I.nnz, sT = (double)dsize(I.ty.T), sX = (double)dsize(I.ty.X);
     const double sV = (double)dsize(I.ty.VI), sP = (double)dsize(I.ty.P);
+    const double sB = I.basis == MPG_BASIS_F16 ? 2.0 : sT;  // an entry of V (2 bytes compressed)
     // Jacobi's diagonal read inside the launch; block Jacobi's own launch
     // after it (w read and written again, bs inverse entries per row)
     const bool bjf = which == 1 ? I.bj_fused_prologue : I.bj_fused_step;
@@ -1056,7 +1121,7 @@ double FusedEngine::phase_bytes(int which) const {
         double cols = 0;
         for (int k = 0; k < I.m; ++k)
             if (I.step_dots_at(k)) cols += k;
-        const double vec = 3 * n * sT + jac * n * sP + cols / I.m * n * sT;
+        const double vec = 2 * n * sT + n * sB + jac * n * sP + cols / I.m * n * sT;
         if (fmt == 2 || fmt == 3) return (double)mpg_arnoldi_sell_matrix_bytes(I.arn) + vec;  // (3: node blocks)
         return z * (sV + 4) + (n + 1) * 4 + vec;
     }
@@ -1069,13 +1134,14 @@ double FusedEngine::phase_bytes(int which) const {
                 cols += (I.orth == MPG_ORTH_MGS ? 1 : k + 1);
                 launches += 1;
             }
-        return (cols / I.m + launches / I.m) * n * sT;
+        return cols / I.m * n * sB + launches / I.m * n * sT;
     }
     // CGS update at mean k: read V(:,0..k), read + write w
-    return ((I.m - 1) / 2.0 + 1) * n * sT + 2 * n * sT;
+    return ((I.m - 1) / 2.0 + 1) * n * sB + 2 * n * sT;
 }
 
 mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
+int FusedEngine::basis() const { return p_->basis; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
 int FusedEngine::prec_fused() const { return p_->bj_bs ? (p_->bj_fused_step ? 1 : 0) : -1; }
 int FusedEngine::prec_sweeps() const { return p_->nm_asked ? p_->nm_asked : -1; }
@@ -1236,6 +1302,10 @@ int mpg_engine_prec_interval(mpg_engine_t e, double* a, double* b) {
 int mpg_engine_accum(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return mpg_arnoldi_accum(e->eng->arnoldi());
+}
+int mpg_engine_basis(mpg_engine_t e) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return mpg_arnoldi_basis(e->eng->arnoldi());
 }
 
 int mpg_engine_prologue_format(mpg_engine_t e) {

@@ -52,6 +52,18 @@ inline void check_neumann_args(const mpg_solve_args& a) { check_sweep_prec_args(
 inline void check_cheb_args(const mpg_solve_args& a) { check_sweep_prec_args(a, "chebyshev"); }
 inline void check_gmres_poly_args(const mpg_solve_args& a) { check_sweep_prec_args(a, "gmres_poly"); }
 
+// The Krylov basis' storage (mpg_arnoldi_set_basis), from the setting
+// MPG_BASIS = f32 (default) / f16 / f16emu, read once when an engine is
+// created; any other value is MPG_ERR_ARG naming it.
+int basis_setting();
+const char* basis_name(int basis);
+// A compressed or emulated basis runs on the fused engine on one GPU, mode
+// mixed, CGS / CGSR, rlen <= 32, CSR or SELL storage (f16emu: CSR), without
+// --orthloss: anything else is MPG_ERR_UNSUPPORTED naming the reason.
+// surface / ranks: the caller is the operator-surface engine / a rank of a
+// row-partitioned solve.
+void check_basis_args(const mpg_solve_args& a, int basis, bool surface, bool ranks);
+
 // Communication seam of the row-partitioned solve: a single-GPU engine has
 // no communicator; a multi-GPU rank supplies one (see comm.hpp).
 class Comm {
@@ -146,6 +158,7 @@ public:
     double time_phase_dup(int which, int reps, int64_t* launches = nullptr, bool step_dots_only = false);
     double phase_bytes(int which) const;
     mpg_arnoldi_t arnoldi() const;
+    int basis() const;  // mpg_engine_basis
     // mixed-half: what the fp16 cast of the Arnoldi values did (stats of
     // mpg_csr_half_values, capi.h; zeros in other modes)
     const int64_t* half_stats() const;

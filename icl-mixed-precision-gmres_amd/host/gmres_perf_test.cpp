@@ -20,7 +20,11 @@
 // Gershgorin bound; the two flags set MPG_CHEB_RATIO / MPG_CHEB_LMAX for this
 // process), --prec gmres_poly [--jacobi-steps S] (the GMRES polynomial of D A
 // from S Arnoldi steps run once at set-up: S roots, no interval and no
-// setting), --device D, --stop-on-breakdown (end the solve with an error at the first
+// setting), --basis {f32,f16,f16emu} (the fused engine's Krylov basis in 2
+// bytes per entry, fp16 of 2^14 v, all arithmetic in the Arnoldi precision:
+// mode mixed, cgs / cgsr, rlen <= 32, one GPU; f16emu the same values as fp32;
+// sets MPG_BASIS for this process, mpg_engine_basis in solve.h),
+// --device D, --stop-on-breakdown (end the solve with an error at the first
 // non-finite Arnoldi residual; without it the count goes to stderr),
 // --ngpus N (row-partition the fused solve over N GPUs of this process, one
 // host thread per GPU, RCCL clique by ncclCommInitAll: mpg_solve_multi_gpu;
@@ -87,6 +91,7 @@ int main(int argc, char* argv[]) {
         else if (f == "--prec-block") a.prec_block = std::stoi(next());
         else if (f == "--cheb-ratio") setenv("MPG_CHEB_RATIO", next(), 1);
         else if (f == "--cheb-lmax") setenv("MPG_CHEB_LMAX", next(), 1);
+        else if (f == "--basis") setenv("MPG_BASIS", next(), 1);
         else if (f == "--gpu") { /* always on the GPU */ }
         else if (f == "--device") a.device = std::stoi(next());
         else if (f == "--ngpus") ngpus = std::stoi(next());

@@ -64,7 +64,8 @@ typedef struct {
     const void* b;         /* outer_type, n */
     void* x;               /* outer_type, row 0 of [-MPG_FRONT_PAD(n_front), n_ext) (halo filled by the caller) */
     int32_t spmv_format;   /* Arnoldi SpMV storage: 0 auto, 1 CSR row blocks, 2 sliced ELL (SELL-64),
-                              3 node blocks (3-dof nodes, 3 x 3 blocks; node_tile.hpp) */
+                              3 node blocks (3-dof nodes, 3 x 3 blocks; node_tile.hpp), 4 auto's choice
+                              among 1 and 2 (what mpg_arnoldi_set_basis's storage types run on) */
     int32_t n_front;       /* halo rows of lower ranks, local ids [-n_front, 0) (0 on one GPU) */
     const int8_t* inner_row_exp; /* inner_val MPG_F16: per-row exponents of the scaled fp16 copy
                                     (mpg_csr_half_values, capi.h), or NULL (unscaled) */
@@ -274,7 +275,9 @@ int mpg_arnoldi_vec_bytes(mpg_arnoldi_t a);             /* sizeof(T) */
  * [4 + k] |s(k+1)| after step k */
 const double* mpg_arnoldi_report_dev(mpg_arnoldi_t a);
 int mpg_arnoldi_report_len(mpg_arnoldi_t a);
-/* The Krylov basis (for tests): V column j of T, ld elements apart */
+/* The Krylov basis (for tests): V column j, ld elements apart; elements of T,
+ * or under MPG_BASIS_F16 (mpg_arnoldi_set_basis) 2-byte fp16 values
+ * rne(2^14 v) */
 const void* mpg_arnoldi_basis_dev(mpg_arnoldi_t a, int64_t* ld);
 const void* mpg_arnoldi_hessenberg_dev(mpg_arnoldi_t a);  /* (m+1) x m, column-major, T */
 /* 1/h_{k+1,k} (T) written by the Givens step k for the next SpMV's
@@ -340,6 +343,34 @@ int mpg_arnoldi_uniform_groups(mpg_arnoldi_t a);
 #define MPG_ACCUM_F32 1
 int mpg_arnoldi_set_accum(mpg_arnoldi_t a, int accum);
 int mpg_arnoldi_accum(mpg_arnoldi_t a);
+
+/* Storage of the Krylov basis V, set once after create, before the first
+ * launch (it reallocates V, zero-filled; a second change of a workspace that
+ * already took F16 or F16EMU is MPG_ERR_ARG):
+ *   MPG_BASIS_F32 (default)  V holds T; every launch form is available.
+ *   MPG_BASIS_F16            the compressed basis: an Arnoldi vector entry
+ *                            v = T(w_prev * inv) is stored as the fp16
+ *                            h = rne(2^14 v), 2 bytes, ld a multiple of 128
+ *                            entries, and used everywhere -- by the operator
+ *                            too: w = M(A v^_k) -- as v^ = 2^-14 float(h).
+ *                            All arithmetic stays in T and the accumulation
+ *                            class. A non-finite v stays non-finite.
+ *   MPG_BASIS_F16EMU         the same v^, stored as fp32 in the F32 layout:
+ *                            the fp32 panel kernels on the rounded values, bit
+ *                            for bit what MPG_BASIS_F16 computes (tests).
+ * Other than F32: an fp32 Arnoldi on fp32 values with an fp64 residual (mode
+ * mixed), CSR row blocks or (F16 only) the SELL copy, else
+ * MPG_ERR_UNSUPPORTED; and the plain launches only -- spmv / givens_spmv /
+ * givens_partials_spmv, dots (CGS / CGSR, k + 1 <= 32), cgs / cgs_partials
+ * (plain CGS from partials, CGSR from sums), reduce, givens*, update (k <=
+ * 32) and the prologue. mgs*, spmv_dots, step_dots, dots_sums, cgs_givens,
+ * cgsr_wide_pass, update_tail, cgs_stream_at, the *_supported queries and the wide (k + 1 > 32)
+ * launches answer MPG_ERR_UNSUPPORTED. */
+#define MPG_BASIS_F32 0
+#define MPG_BASIS_F16 1
+#define MPG_BASIS_F16EMU 2
+int mpg_arnoldi_set_basis(mpg_arnoldi_t a, int basis);
+int mpg_arnoldi_basis(mpg_arnoldi_t a);
 
 /* Storage the residual prologue runs on: 1 CSR row blocks, 2 the SELL copy
  * of the outer values, 3 node blocks (row sums on the node copy, then the

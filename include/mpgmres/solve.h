@@ -254,6 +254,17 @@ int mpg_engine_prec_roots(mpg_engine_t e, double* re, double* im, int32_t cap);
 int mpg_gmres_poly_roots(int s, const double* H, int ldh, double* re, double* im, int* count);
 /* the accumulation class the engine's Arnoldi runs: MPG_ACCUM_F64 0 / MPG_ACCUM_F32 1 (arnoldi.h) */
 int mpg_engine_accum(mpg_engine_t e);
+/* The storage of the engine's Krylov basis: MPG_BASIS_F32 0 / MPG_BASIS_F16 1 / MPG_BASIS_F16EMU 2
+ * (mpg_arnoldi_set_basis, arnoldi.h). Chosen by the setting MPG_BASIS = f32 (default) / f16 / f16emu, read once when
+ * the engine is created (any other value: MPG_ERR_ARG naming it). f16 stores each basis entry in 2 bytes (fp16 of
+ * 2^14 v) and keeps all arithmetic in the Arnoldi precision; it costs at most about 2^-11 of orthonormality per
+ * cycle (a cycle cannot reduce the residual by more than ~2.5e-4). It runs on the fused engine on one GPU, mode mixed,
+ * orth cgs / cgsr, rlen <= 32, CSR or SELL storage (auto picks among the two), with every preconditioner and the
+ * base and rtol strategies, in the plain launch forms (as under MPG_STEP_DOTS=0 MPG_CGS_PREFETCH=0 MPG_TAIL_FOLD=0;
+ * asking for a fused form is MPG_ERR_UNSUPPORTED). Anything else -- another mode, mgs, rlen > 32, --orthloss, forced
+ * node blocks, a row-partitioned engine, the operator-surface engine, f16emu on SELL -- is MPG_ERR_UNSUPPORTED with
+ * the reason in the message. f16emu: the same values held as fp32, for tests. */
+int mpg_engine_basis(mpg_engine_t e);
 /* the residual prologue's storage (mpg_arnoldi_prologue_format: 1 CSR, 2 SELL, 3 node blocks) */
 int mpg_engine_prologue_format(mpg_engine_t e);
 /* ranks of the engine's communicator as its transport reports them: 1 for a
