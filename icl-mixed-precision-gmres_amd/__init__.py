@@ -224,6 +224,12 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_sell_shared_slices.argtypes = [C.c_void_p]
     lib.mpg_engine_sell_shared_slices.restype = C.c_int64
     lib.mpg_engine_sell_sigma.argtypes = [C.c_void_p]
+    lib.mpg_solve_from.argtypes = [C.POINTER(SolveArgs), C.c_void_p, C.POINTER(SolveResult)]
+    lib.mpg_solve_from.restype = C.c_int
+    lib.mpg_engine_rearm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.mpg_engine_x.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.mpg_engine_solves.argtypes = [C.c_void_p]
+    lib.mpg_engine_graph_captures.argtypes = [C.c_void_p]
 
 
 # (name, argtypes) for the kernel-level C-ABI, used by the per-kernel tests
@@ -646,10 +652,66 @@ def run_solve(fn, args: SolveArgs, n: int, cycle_cap: int = 4096, step_cap: int 
                   nonfinite_cycles=r.nonfinite_cycles, first_nonfinite_step=r.first_nonfinite_step)
 
 
-def solve(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, **opts) -> Result:
-    """Restarted GMRES(m) on the MI355X (mpg_solve). Options as make_args."""
+ARM_B_DEVICE, ARM_X0_DEVICE = 1, 2  # MPG_ARM_B_DEVICE, MPG_ARM_X0_DEVICE (solve.h)
+
+
+def _is_tensor(v) -> bool:
+    import sys
+
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(v, torch.Tensor)
+
+
+def _arm_vector(v, n: int, device: int, name: str, host_only: bool = False, writable: bool = False):
+    """A vector handed to a live engine: (address, on_device, what keeps it
+    alive). NumPy: anything that converts to a 1-D fp64 array of n (copied
+    where it is not one already; an output must be one). A torch tensor: fp64,
+    contiguous, of length n, on the engine's device -- its address is passed
+    as it is, after torch's current stream on that device has completed.
+    Anything else is a ValueError, raised before any call into the library."""
+    if _is_tensor(v):
+        import torch
+
+        if host_only:
+            raise ValueError(f"{name}: a host array is expected (it is read on the host), not a torch tensor")
+        if v.dtype != torch.float64:
+            raise ValueError(f"{name}: a tensor must be float64, not {v.dtype}")
+        if v.dim() != 1 or v.numel() != n:
+            raise ValueError(f"{name}: a tensor of shape {tuple(v.shape)} where ({n},) is expected")
+        if not v.is_contiguous():
+            raise ValueError(f"{name}: a tensor must be contiguous (stride {v.stride()})")
+        if not v.is_cuda or v.device.index != device:
+            raise ValueError(f"{name}: a tensor must live on the engine's device cuda:{device}, not {v.device}")
+        torch.cuda.current_stream(v.device).synchronize()
+        return v.data_ptr(), True, v
+    if writable:
+        if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.flags.writeable):
+            raise ValueError(f"{name}: an output must be a writable contiguous float64 array")
+        a = v
+    else:
+        try:
+            a = np.ascontiguousarray(v, dtype=np.float64)
+        except (TypeError, ValueError) as ex:
+            raise ValueError(f"{name}: not convertible to a float64 array ({ex})") from None
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(f"{name}: an array of shape {a.shape} where ({n},) is expected")
+    return a.ctypes.data, False, a
+
+
+def solve(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, x0=None, **opts) -> Result:
+    """Restarted GMRES(m) on the MI355X (mpg_solve). Options as make_args.
+    x0: an initial guess (host array of n; None: zeros), through
+    mpg_solve_from -- fused engine only. Like `basis` it is not a field of
+    mpg_solve_args: it rides on the structure as `_x0`."""
     args, keep = make_args(A, b, x_true, **opts)
-    return run_solve(host_lib().mpg_solve, args, A.nrows)
+    args._x0 = None
+    if x0 is None:
+        return run_solve(host_lib().mpg_solve, args, A.nrows)
+    if _is_tensor(x0):
+        raise ValueError("x0: solve() takes a host array (Engine.solve takes device tensors)")
+    ptr, _, args._x0 = _arm_vector(x0, A.nrows, args.device, "x0")
+    lib = host_lib()
+    return run_solve(lambda a, r: lib.mpg_solve_from(a, ptr, r), args, A.nrows)
 
 
 def cycle_program_counts() -> dict:
@@ -902,6 +964,81 @@ class Engine:
                                                                rank, C.byref(self._h), err, 512)
         if st:
             raise RuntimeError(f"mpg_engine_create: {err.value.decode()}")
+        self._done = False
+
+    def rearm(self, b=None, x0=None, x_true=None) -> None:
+        """Start another solve on this engine (mpg_engine_rearm): a new
+        right-hand side (None: keep the current one), an initial guess (None:
+        zeros) and a new x_true for err_norm (host; None: none). b and x0 are
+        NumPy arrays or fp64 torch tensors on the engine's device (read in
+        place). The matrix copies, the preconditioner, the cycle policy and
+        the captured graph are kept; the solve that follows has the bits of a
+        new engine's. ValueError: a vector of the wrong type, length or
+        device, before anything is touched. RuntimeError with the status:
+        a row-partitioned engine, or one that ran time_phase*."""
+        n, dev = self._args.n, self._args.device
+        flags = 0
+        ptrs, keep = [], []
+        for v, name, flag in ((b, "b", ARM_B_DEVICE), (x0, "x0", ARM_X0_DEVICE), (x_true, "x_true", 0)):
+            if v is None:
+                ptrs.append(None)
+                continue
+            ptr, on_dev, k = _arm_vector(v, n, dev, name, host_only=name == "x_true")
+            flags |= flag if on_dev else 0
+            ptrs.append(ptr)
+            keep.append(k)
+        st = self._lib.mpg_engine_rearm(self._h, ptrs[0], ptrs[1], ptrs[2], flags)
+        if st:
+            msg = self._lib.mpg_engine_last_error(self._h).decode(errors="replace")
+            raise RuntimeError(f"mpg_engine_rearm failed ({st}): {msg}")
+        self._done = False
+
+    def solve(self, b=None, x0=None, x_true=None, max_cycles: Optional[int] = None, cycle_cap: int = 4096,
+              step_cap: int = 1 << 17) -> Result:
+        """One solve on the live engine: re-arm if any of b, x0, x_true is
+        given (rearm), run until done or for at most max_cycles restart
+        cycles, and report. Without arguments it finishes the solve the engine
+        is armed with (the constructor's, or the last rearm's); a finished
+        solve is only reported again. gmres_seconds: the run, timed here."""
+        import time
+
+        if b is not None or x0 is not None or x_true is not None:
+            self.rearm(b, x0, x_true)
+        t0 = time.perf_counter()
+        left = max_cycles
+        while not self._done and (left is None or left > 0):
+            ran, self._done = self.run((1 << 20) if left is None else left)
+            if left is not None:
+                left -= max(ran, 1)
+        self.sync()
+        dt = time.perf_counter() - t0
+        res = self.report(cycle_cap, step_cap)
+        res.gmres_seconds = dt
+        return res
+
+    def x(self, out=None):
+        """Rows [0, n) of the iterate widened to fp64 (mpg_engine_x): a new
+        NumPy array, or `out` filled and returned -- a float64 NumPy array or
+        an fp64 torch tensor on the engine's device."""
+        n = self._args.n
+        if out is None:
+            out = np.empty(n, dtype=np.float64)
+        ptr, on_dev, _ = _arm_vector(out, n, self._args.device, "out", writable=True)
+        st = self._lib.mpg_engine_x(self._h, ptr, int(on_dev))
+        if st:
+            msg = self._lib.mpg_engine_last_error(self._h).decode(errors="replace")
+            raise RuntimeError(f"mpg_engine_x failed ({st}): {msg}")
+        return out
+
+    @property
+    def solves(self) -> int:
+        """Solves armed on this engine so far, the constructor's included (mpg_engine_solves)."""
+        return int(self._lib.mpg_engine_solves(self._h))
+
+    @property
+    def graph_captures(self) -> int:
+        """Cycle graphs captured so far (mpg_engine_graph_captures): at most 1, however many solves ran."""
+        return int(self._lib.mpg_engine_graph_captures(self._h))
 
     @classmethod
     def distributed(cls, A_local: Csr, b_local, x_true_local, plan: HaloPlan, uid: bytes, nranks: int, rank: int,
@@ -929,6 +1066,7 @@ class Engine:
         if ran < 0:
             msg = self._lib.mpg_engine_last_error(self._h).decode(errors="replace")
             raise RuntimeError(f"mpg_engine_run failed ({ran}): {msg}")
+        self._done = bool(done.value)
         return ran, bool(done.value)
 
     def sync(self) -> None:

@@ -153,6 +153,10 @@ struct FusedEngine::Impl {
     // cycle's report is read; it starts by saving x, so a cycle launched past
     // a stop decision is undone by restoring x
     DevMem x_snap;
+    // arming (FusedEngine::arm): host fp64 vectors pass through stage64 where x
+    // is not fp64; x_true is kept on the device for finish_report
+    DevMem stage64, xt;
+    bool have_xt = false;
     hipEvent_t report_ev[2] = {nullptr, nullptr};
     CyclePolicy pol{};      // what decides the cycle's launches (resolve_policy)
     std::vector<Op> cycle;  // plan_cycle(pol): the ops of one restart cycle
@@ -389,7 +393,7 @@ void FusedEngine::Impl::resolve_policy() {
                               "launch supports)");
 }
 
-FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int n_ext, int n_front)
+FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int n_ext, int n_front, const double* x0)
     : p_(new Impl) {
     auto t0 = clk::now();
     Impl& I = *p_;
@@ -562,39 +566,14 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     // ILU(0) of the fp64 A in the preconditioner precision (gmres_perf_test.cpp:70-79, 140-149)
     if (ilu) check(mpg_ilu0_create(ctx, I.csr, I.val64.as<double>(), ty.P == MPG_F64 ? 0 : 1, &I.ilu), "ilu0", ctx);
 
-    // b (outer type), x = 0 (outer type, with halo tail)
-    DevMem b64(ctx, (size_t)I.n * 8 + 8);
-    check(mpg_memcpy_h2d(ctx, b64.p, a.b, (size_t)I.n * 8), "h2d", ctx);
-    if (ty.X == MPG_F64) {
-        I.b = std::move(b64);
-    } else {
-        I.b = DevMem(ctx, (size_t)I.n * 4 + 8);
-        I.cast(b64.p, MPG_F64, I.b.p, MPG_F32, I.n);
-    }
+    // b and x (outer type, x with halo tail), the work vectors of the arm
+    // (tmp_t: T(b), tmp_p: typesafe_apply's P copy); their values are arm()'s
+    I.b = DevMem(ctx, (size_t)I.n * dsize(ty.X) + 8);
+    if (ty.X != MPG_F64) I.stage64 = DevMem(ctx, (size_t)I.n * 8 + 8);
     I.x = DevMem(ctx, (size_t)(I.front + I.n_ext) * dsize(ty.X) + 64);
     I.xp = static_cast<char*>(I.x.p) + (size_t)I.front * dsize(ty.X);
-
-    // one-time norms of the drivers (gmres.cpp:51-58, 162-168)
-    b_norm = I.nrm2(I.b.p, ty.X, I.n);
-    {
-        I.tmp_t = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
-        I.cast(I.b.p, ty.X, I.tmp_t.p, ty.T, I.n);  // copy(b, w)
-        if (ty.P != ty.T) {                             // typesafe_apply
-            I.tmp_p = DevMem(ctx, (size_t)I.n * dsize(ty.P) + 64);
-            I.cast(I.tmp_t.p, ty.T, I.tmp_p.p, ty.P, I.n);
-        }
-        void* wp = ty.P != ty.T ? I.tmp_p.p : I.tmp_t.p;
-        if (I.jacobi_inside()) {
-            if (ty.P == MPG_F64)
-                check(mpg_gdmv_f64(ctx, I.n, 1.0, I.diag.as<double>(), (double*)wp, 0.0, (double*)wp), "gdmv", ctx);
-            else
-                check(mpg_gdmv_f32(ctx, I.n, 1.0f, I.diag.as<float>(), (float*)wp, 0.0f, (float*)wp), "gdmv", ctx);
-        }
-        if (I.ilu) I.solve_ilu(wp);
-        if (ty.P != ty.T) I.cast(I.tmp_p.p, ty.P, I.tmp_t.p, ty.T, I.n);
-        if (I.bj_bs) I.apply_bjacobi(I.tmp_t.p);  // (on the vector of T, casting inside)
-        minvb_norm = I.nrm2(I.tmp_t.p, ty.T, I.n);
-    }
+    I.tmp_t = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
+    if (ty.P != ty.T) I.tmp_p = DevMem(ctx, (size_t)I.n * dsize(ty.P) + 64);
     // ||A||_F of the matrix the driver was given (A_single in mixed mode)
     {
         const bool mixed = !rounded_outer;
@@ -648,12 +627,8 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     // fp32 Arnoldi: the reference's fp32 accumulation class on request (arnoldi.h)
     if (a.accum) check(mpg_arnoldi_set_accum(I.arn, MPG_ACCUM_F32), "mpg_arnoldi_set_accum", ctx);
     if (I.basis != MPG_BASIS_F32) check(mpg_arnoldi_set_basis(I.arn, I.basis), "mpg_arnoldi_set_basis", ctx);
-    if (I.nm_steps) {  // ||M^-1 b|| through the launches every application takes (tmp_t still holds T(b))
-        if (I.nm_steps >= 2) I.nm_work0 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
-        if (I.nm_steps >= 3) I.nm_work1 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
-        I.apply_neumann(I.tmp_t.p);
-        minvb_norm = I.nrm2(I.tmp_t.p, ty.T, I.n);
-    }
+    if (I.nm_steps >= 2) I.nm_work0 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
+    if (I.nm_steps >= 3) I.nm_work1 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
     // ranks all-reduce per-workgroup partials in place: same count on every rank
     // (MPG_UNIFORM_GROUPS=1 gives one GPU the ranks' partial counts: a P = 1
     // RCCL solve then has the single-GPU solve's bits, tests/test_dist_gpu.py)
@@ -664,34 +639,157 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     I.report_host = I.rep[0];
     for (hipEvent_t& e : I.report_ev) hipck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "event");
 
+    if (I.orthloss) {
+        const size_t mm = (size_t)a.rlen;
+        I.loss_S = DevMem(ctx, (size_t)(mm + 1) * (mm + 1) * dsize(ty.T));
+        I.loss_u = DevMem(ctx, (size_t)(mm + 2) * dsize(ty.T));
+    }
+    breakdown.stop = a.stop_on_breakdown != 0;
+
+    I.resolve_policy();
+    if (I.pol.pipeline) I.x_snap = DevMem(ctx, I.x.bytes);
+    if (I.pol.pipeline && tail_fold())
+        check(mpg_arnoldi_set_x_snapshot(I.arn, static_cast<char*>(I.x_snap.p) + (size_t)I.front * dsize(I.ty.X)),
+              "x snapshot", ctx);
+    arm(a.b, x0, a.x_true, 0);
+    check(mpg_ctx_sync(ctx), "sync", ctx);
+    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
+    start();
+}
+
+// What a solve takes from b and x: the vectors in the outer type, the drivers'
+// one-time norms of b and M^-1 b, x_true for the report, and the host's
+// per-solve state. The constructor and rearm() both come through here, so a
+// re-armed solve runs a fresh engine's launches on a fresh engine's values.
+// b: nullptr keeps the current right-hand side (rearm only); x0: nullptr is
+// zeros; flags: MPG_ARM_B_DEVICE / MPG_ARM_X0_DEVICE (solve.h).
+void FusedEngine::arm(const double* b, const double* x0, const double* x_true, int flags) {
+    Impl& I = *p_;
+    const mpg_ctx_t ctx = I.ctx;
+    const ModeTypes& ty = I.ty;
+    const size_t n8 = (size_t)I.n * 8;
+    // an fp64 vector of n, in host memory or on the device, into a device vector of the outer type
+    auto put = [&](const double* src, bool on_device, void* dst) {
+        if (on_device) {
+            if (ty.X == MPG_F64) check(mpg_memcpy_d2d(ctx, dst, src, n8), "d2d", ctx);
+            else I.cast(src, MPG_F64, dst, ty.X, I.n);
+            return;
+        }
+        void* to = ty.X == MPG_F64 ? dst : I.stage64.p;
+        check(mpg_memcpy_h2d(ctx, to, src, n8), "h2d", ctx);
+        if (ty.X != MPG_F64) I.cast(I.stage64.p, MPG_F64, dst, ty.X, I.n);
+    };
+    if (b) put(b, (flags & MPG_ARM_B_DEVICE) != 0, I.b.p);
+    // x: zeros in the front pad, the halo and the tail, X(x0) over rows [0, n)
+    // (the first arm finds the allocation's zeros)
+    if (solves_ > 0) check(mpg_memset(ctx, I.x.p, 0, I.x.bytes), "memset", ctx);
+    if (x0) put(x0, (flags & MPG_ARM_X0_DEVICE) != 0, I.xp);
+    I.have_xt = x_true != nullptr;
+    if (x_true) {
+        if (!I.xt.p) I.xt = DevMem(ctx, n8 + 8);  // (the first x_true this engine is given)
+        check(mpg_memcpy_h2d(ctx, I.xt.p, x_true, n8), "h2d", ctx);
+    }
+
+    // one-time norms of the drivers (gmres.cpp:51-58, 162-168)
+    b_norm = I.nrm2(I.b.p, ty.X, I.n);
+    {
+        I.cast(I.b.p, ty.X, I.tmp_t.p, ty.T, I.n);              // copy(b, w)
+        if (ty.P != ty.T) I.cast(I.tmp_t.p, ty.T, I.tmp_p.p, ty.P, I.n);  // typesafe_apply
+        void* wp = ty.P != ty.T ? I.tmp_p.p : I.tmp_t.p;
+        if (I.jacobi_inside()) {
+            if (ty.P == MPG_F64)
+                check(mpg_gdmv_f64(ctx, I.n, 1.0, I.diag.as<double>(), (double*)wp, 0.0, (double*)wp), "gdmv", ctx);
+            else
+                check(mpg_gdmv_f32(ctx, I.n, 1.0f, I.diag.as<float>(), (float*)wp, 0.0f, (float*)wp), "gdmv", ctx);
+        }
+        if (I.ilu) I.solve_ilu(wp);
+        if (ty.P != ty.T) I.cast(I.tmp_p.p, ty.P, I.tmp_t.p, ty.T, I.n);
+        if (I.bj_bs) I.apply_bjacobi(I.tmp_t.p);  // (on the vector of T, casting inside)
+        // the sweeps: ||M^-1 b|| through the launches every application takes (tmp_t holds T(b))
+        if (I.nm_steps) I.apply_neumann(I.tmp_t.p);
+        minvb_norm = I.nrm2(I.tmp_t.p, ty.T, I.n);
+    }
+    if (I.pol.pipeline && tail_fold()) {
+        // the givens+update launch keeps rows [0, n) of the x it reads; the
+        // restore copies the whole array, so its padding is filled here
+        hipck(hipMemcpyAsync(I.x_snap.p, I.x.p, I.x.bytes, hipMemcpyDeviceToDevice, I.stream()), "x snapshot");
+    }
+
+    // the host's state of a solve
+    cycles.clear();
+    step_res.clear();
+    step_cycle.clear();
+    status = 0;
+    restarts = 0;
+    inner_k = 0;
+    const bool stop = breakdown.stop;
+    breakdown = BreakdownLog();
+    breakdown.stop = stop;
+    I.report_host = I.rep[0];
     // convergence strategy (gmres_perf_test.cpp:185-196)
+    const mpg_solve_args& a = I.args;
     const size_t mm = (size_t)a.rlen, mr = (size_t)a.max_restarts;
     if (a.rtol == 0) conv_ = std::make_unique<Convergence<double, void>>(a.tol, mm, mr);
     else if (a.repeat_iter) conv_ = std::make_unique<RepeatIteration_Convergence<double, void>>(a.tol, a.rtol, mm, mr);
     else if (I.orthloss) {
         auto lo = std::make_unique<LostOrthogonalityFused>(a.tol, a.rtol, mm, mr);
         lo->step_loss = [this](size_t k) { return orth_loss_step(k); };
-        I.loss_S = DevMem(ctx, (size_t)(mm + 1) * (mm + 1) * dsize(ty.T));
-        I.loss_u = DevMem(ctx, (size_t)(mm + 2) * dsize(ty.T));
+        if (solves_ > 0) {
+            // S, u and the basis as a new engine has them: the loss estimate
+            // reads the basis column after the newest one (orth_loss_step)
+            int64_t ld = 0;
+            void* V = const_cast<void*>(mpg_arnoldi_basis_dev(I.arn, &ld));
+            check(mpg_memset(ctx, V, 0, (size_t)ld * (mm + 1) * dsize(ty.T)), "memset", ctx);
+            check(mpg_memset(ctx, I.loss_S.p, 0, I.loss_S.bytes), "memset", ctx);
+            check(mpg_memset(ctx, I.loss_u.p, 0, I.loss_u.bytes), "memset", ctx);
+        }
         conv_ = std::move(lo);
     } else conv_ = std::make_unique<RelPrecRes_Convergence<double, void>>(a.tol, a.rtol, mm, mr);
     conv_->total_iters = 0;
-    breakdown.stop = a.stop_on_breakdown != 0;
+    ++solves_;
+}
 
-    I.resolve_policy();
-    if (I.pol.pipeline) I.x_snap = DevMem(ctx, I.x.bytes);
-    if (I.pol.pipeline && tail_fold()) {
-        // the givens+update launch keeps rows [0, n) of the x it reads; the
-        // restore copies the whole array, so its padding is filled here, once
-        hipck(hipMemcpyAsync(I.x_snap.p, I.x.p, I.x.bytes, hipMemcpyDeviceToDevice, I.stream()), "x snapshot");
-        check(mpg_arnoldi_set_x_snapshot(I.arn, static_cast<char*>(I.x_snap.p) + (size_t)I.front * dsize(I.ty.X)),
-              "x snapshot", ctx);
-    }
-    check(mpg_ctx_sync(ctx), "sync", ctx);
-    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
+void FusedEngine::start() {
     prologue();
     read_report(4);
-    if (I.ilu) check_ilu_fault(I.ilu);
+    if (p_->ilu) check_ilu_fault(p_->ilu);
+}
+
+namespace {
+const char* const kMeasuredText =
+    "the engine ran measurement launches (mpg_engine_time_*), which change its Krylov basis, "
+    "Hessenberg column and iterate; create a new engine to continue a solve";
+}
+
+void FusedEngine::rearm(const double* b, const double* x0, const double* x_true, int flags) {
+    Impl& I = *p_;
+    if (I.comm)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          "re-arming a row-partitioned engine is not available: the norms of the new vectors and "
+                          "the halo of the initial guess would have to cross the ranks");
+    if (measured) throw StatusError(MPG_ERR_UNSUPPORTED, kMeasuredText);
+    auto t0 = clk::now();
+    arm(b, x0, x_true, flags);
+    check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
+    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
+    start();
+}
+
+void FusedEngine::copy_x(double* dst, bool dst_on_device) {
+    Impl& I = *p_;
+    const size_t n8 = (size_t)I.n * 8;
+    if (dst_on_device) {
+        if (I.ty.X == MPG_F64) check(mpg_memcpy_d2d(I.ctx, dst, I.xp, n8), "d2d", I.ctx);
+        else I.cast(I.xp, I.ty.X, dst, MPG_F64, I.n);
+    } else {
+        const void* from = I.xp;
+        if (I.ty.X != MPG_F64) {
+            I.cast(I.xp, I.ty.X, I.stage64.p, MPG_F64, I.n);
+            from = I.stage64.p;
+        }
+        check(mpg_memcpy_d2h(I.ctx, dst, from, n8), "d2h", I.ctx);
+    }
+    sync();
 }
 
 FusedEngine::~FusedEngine() = default;
@@ -914,6 +1012,7 @@ void FusedEngine::ensure_graph() {
     if (!I.pol.graph || I.graph.exec) return;
     try {
         I.graph = CapturedGraph(I.stream(), [this] { issue(p_->cycle); });
+        ++graph_captures_;
     } catch (const std::exception& ex) {
         std::fprintf(stderr, "mpgmres: cycle capture failed (%s); running eagerly\n", ex.what());
         I.pol.graph = 0;
@@ -983,9 +1082,7 @@ int FusedEngine::run_pipelined(int max_cycles, bool& done) {
 // MPG_ERR_BREAKDOWN (nothing left in flight: a pipelined cycle may be)
 int FusedEngine::run(int max_cycles, bool& done) {
     if (measured)
-        throw StatusError(MPG_ERR_UNSUPPORTED,
-                          "the engine ran measurement launches (mpg_engine_time_*), which change its Krylov basis, "
-                          "Hessenberg column and iterate; create a new engine to continue a solve");
+        throw StatusError(MPG_ERR_UNSUPPORTED, kMeasuredText);
     try {
         return run_cycles(max_cycles, done);
     } catch (const BreakdownError& e) {
@@ -1070,10 +1167,8 @@ void FusedEngine::finish_report(mpg_solve_result* r) {
     check(mpg_memcpy_d2d(I.ctx, r64.p, b64.p, (size_t)n * 8), "d2d", I.ctx);
     check(mpg_csr_spmv_f64(I.ctx, I.csr, -1.0, I.val64.as<double>(), x64, 1.0, r64.as<double>()), "spmv", I.ctx);
     r->res_norm = std::sqrt(I.dot_acc(r64.p, r64.p, MPG_F64, n));
-    if (I.args.x_true) {
-        DevMem xt(I.ctx, (size_t)n * 8 + 8);
-        check(mpg_memcpy_h2d(I.ctx, xt.p, I.args.x_true, (size_t)n * 8), "h2d", I.ctx);
-        check(mpg_axpy_f64(I.ctx, n, -1.0, xt.as<double>(), x64), "axpy", I.ctx);
+    if (I.have_xt) {  // (the copy arm() made: the caller's array may be gone)
+        check(mpg_axpy_f64(I.ctx, n, -1.0, I.xt.as<double>(), x64), "axpy", I.ctx);
         r->err_norm = std::sqrt(I.dot_acc(x64, x64, MPG_F64, n));
     }
 }
@@ -1202,12 +1297,12 @@ void fill_history(const FusedEngine& e, mpg_solve_result* r) {
     }
 }
 
-int solve_fused(const mpg_solve_args& a, mpg_solve_result* r) {
+int solve_fused(const mpg_solve_args& a, mpg_solve_result* r, const double* x0) {
     mpg_ctx_t ctx = current_ctx();
     const char* banner = a.mode == MPG_MODE_MIXED || a.mode == MPG_MODE_MIXED_HALF ? "Doing Mixed Precision test"
                                                                                      : "Doing Baseline test";
     out() << banner << std::endl;
-    FusedEngine e(ctx, a);
+    FusedEngine e(ctx, a, nullptr, -1, 0, x0);
     auto t1 = clk::now();
     bool done = false;
     while (!done) e.run(1 << 20, done);
@@ -1256,6 +1351,25 @@ int mpg_engine_run(mpg_engine_t e, int max_cycles, int* done) {
 }
 
 const char* mpg_engine_last_error(mpg_engine_t e) { return e ? e->last_error.c_str() : ""; }
+
+int mpg_engine_rearm(mpg_engine_t e, const double* b, const double* x0, const double* x_true, int flags) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return mpg::engine_call(e, [&] {
+        e->eng->rearm(b, x0, x_true, flags);
+        return (int)MPG_OK;
+    });
+}
+
+int mpg_engine_x(mpg_engine_t e, double* dst, int dst_on_device) {
+    if (!e || !e->eng || !dst) return MPG_ERR_ARG;
+    return mpg::engine_call(e, [&] {
+        e->eng->copy_x(dst, dst_on_device != 0);
+        return (int)MPG_OK;
+    });
+}
+
+int mpg_engine_solves(mpg_engine_t e) { return e && e->eng ? e->eng->solves() : MPG_ERR_ARG; }
+int mpg_engine_graph_captures(mpg_engine_t e) { return e && e->eng ? e->eng->graph_captures() : MPG_ERR_ARG; }
 
 int mpg_engine_sync(mpg_engine_t e) {
     if (!e) return MPG_ERR_ARG;

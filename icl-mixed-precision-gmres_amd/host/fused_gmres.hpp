@@ -143,13 +143,30 @@ public:
     // (global columns already remapped to [0, n_ext)); a single GPU passes the
     // whole matrix and no communicator.
     // n_front: halo rows of lower ranks, local ids [-n_front, 0) (dist.h)
-    FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& args, Comm* comm = nullptr, int n_ext = -1, int n_front = 0);
+    // x0: the initial guess (host fp64, n; one GPU only), nullptr: zeros
+    FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& args, Comm* comm = nullptr, int n_ext = -1, int n_front = 0,
+                const double* x0 = nullptr);
     ~FusedEngine();
 
     // Advance the solve by up to max_cycles outer iterations; returns the
     // number run. `done` is set on convergence or abort.
     int run(int max_cycles, bool& done);
     void finish_report(mpg_solve_result* r);  // resNorm/errNorm + x with the original fp64 A
+
+    // Start another solve on this engine (mpg_engine_rearm, solve.h): a new
+    // right-hand side (b == nullptr: keep the current one), an initial guess
+    // (x0 == nullptr: zeros) and a new x_true (host, may be nullptr), through
+    // the code the constructor arms its own solve with. b / x0 are fp64
+    // arrays of n in host memory, or on the engine's device where `flags`
+    // says so (MPG_ARM_B_DEVICE, MPG_ARM_X0_DEVICE). The matrix copies, the
+    // preconditioner, the policy, the captured cycle and every buffer stay as
+    // they are. Refused (MPG_ERR_UNSUPPORTED) on a row-partitioned engine and
+    // after measurement launches.
+    void rearm(const double* b, const double* x0, const double* x_true, int flags);
+    // rows [0, n) of x widened to fp64 into dst (host, or the engine's device); synchronises
+    void copy_x(double* dst, bool dst_on_device);
+    int solves() const { return solves_; }                  // arms so far, the constructor's included
+    int graph_captures() const { return graph_captures_; }  // cycle graphs captured so far
 
     size_t total_iters() const { return conv_->total_iterations(); }
     double time_phase(int which, int reps, bool inplace = false, std::vector<double>* per_launch = nullptr);
@@ -192,6 +209,10 @@ private:
     struct Impl;
     std::unique_ptr<Impl> p_;
     std::unique_ptr<Convergence<double, void>> conv_;
+    int solves_ = 0, graph_captures_ = 0;
+    // what depends on b and x: the constructor's and rearm's one code path
+    void arm(const double* b, const double* x0, const double* x_true, int flags);
+    void start();  // the first residual prologue of a solve and its report
     void prologue();
     void step(int k, bool fold);
     void issue(const Op& op);
@@ -213,7 +234,8 @@ private:
     bool check_start(int64_t i);
 };
 
-int solve_fused(const mpg_solve_args& args, mpg_solve_result* result);
+// x0: the initial guess (host fp64, n), nullptr: zeros (mpg_solve_from)
+int solve_fused(const mpg_solve_args& args, mpg_solve_result* result, const double* x0 = nullptr);
 // status, counts and the per-cycle / per-step history of an engine into r
 void fill_history(const FusedEngine& e, mpg_solve_result* r);
 

@@ -28,7 +28,13 @@
 // non-finite Arnoldi residual; without it the count goes to stderr),
 // --ngpus N (row-partition the fused solve over N GPUs of this process, one
 // host thread per GPU, RCCL clique by ncclCommInitAll: mpg_solve_multi_gpu;
-// devices --device .. --device+N-1; fails when fewer GPUs are visible).
+// devices --device .. --device+N-1; fails when fewer GPUs are visible),
+// --solves N (N systems with the one matrix on one fused engine, set up once:
+// mpg_engine_create, then mpg_engine_rearm per further system; the stdout
+// block is printed once per solve; solve j takes x_true from --rand + j, or
+// the --bpath vector every time; without the flag, or with N = 1, the one
+// solve through mpg_solve as before).
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,6 +73,7 @@ int main(int argc, char* argv[]) {
     a.verbose = 1;
     unsigned rand_seed = 42;
     int ngpus = 0;  // 0: mpg_solve on one device
+    int solves = 1;
 
     for (int i = 1; i < argc; ++i) {
         const std::string f = argv[i];
@@ -95,6 +102,7 @@ int main(int argc, char* argv[]) {
         else if (f == "--gpu") { /* always on the GPU */ }
         else if (f == "--device") a.device = std::stoi(next());
         else if (f == "--ngpus") ngpus = std::stoi(next());
+        else if (f == "--solves") solves = std::stoi(next());
         else if (f == "--half-unscaled") a.half_unscaled = 1;
         else if (f == "--stop-on-breakdown") a.stop_on_breakdown = 1;
         else if (f == "--accum") {  // fp32 Arnoldi's accumulation class (solve.h)
@@ -155,6 +163,19 @@ int main(int argc, char* argv[]) {
         std::cout << "No value suplied for A" << std::endl;
         return 1;
     }
+    if (solves < 1) {
+        std::cout << "--solves takes a positive number of systems" << std::endl;
+        return 1;
+    }
+    if (solves > 1 && (a.engine != MPG_ENGINE_FUSED || ngpus >= 1)) {
+        // (the library's rule: mpg_engine_rearm exists on the fused engine, on one GPU)
+        std::cerr << "mpg_solve failed: mpgmres: a sequence of solves on one engine (--solves) runs on the fused "
+                     "engine on one GPU only: "
+                  << (a.engine != MPG_ENGINE_FUSED ? "the operator surface's drivers set up one solve per call"
+                                                   : "re-arming a row-partitioned engine is not available")
+                  << std::endl;
+        return 1;
+    }
 
     mpg_host_csr A{};
     char err[256] = {0};
@@ -183,9 +204,12 @@ int main(int argc, char* argv[]) {
         }
     }
 
-    std::cout << "||x|| = " << host_nrm2(x_true.data(), n) << std::endl;
-    std::cout << "||b|| = " << host_nrm2(b.data(), n) << std::endl;
-    std::cout << "||A|| = " << host_nrm2(A.val, A.nnz) << std::endl;
+    auto print_norms = [&] {
+        std::cout << "||x|| = " << host_nrm2(x_true.data(), n) << std::endl;
+        std::cout << "||b|| = " << host_nrm2(b.data(), n) << std::endl;
+        std::cout << "||A|| = " << host_nrm2(A.val, A.nnz) << std::endl;
+    };
+    print_norms();
 
     a.n = (int32_t)n;
     a.nnz = A.nnz;
@@ -195,8 +219,48 @@ int main(int argc, char* argv[]) {
     a.b = b.data();
     a.x_true = x_true.data();
     mpg_solve_result r{};
-    int st;
-    if (ngpus >= 1 && !(ngpus == 1 && a.engine != MPG_ENGINE_FUSED)) {
+    int st = 0;
+    if (solves > 1) {
+        // one engine, set up once; every further system re-arms it (solve.h)
+        const char* banner = a.mode == MPG_MODE_MIXED || a.mode == MPG_MODE_MIXED_HALF ? "Doing Mixed Precision test"
+                                                                                         : "Doing Baseline test";
+        mpg_engine_t eng = nullptr;
+        for (int j = 0; j < solves && st == 0; ++j) {
+            if (j > 0) {
+                if (!b_path) {
+                    mpg_rand_vect(n, rand_seed + (unsigned)j, x_true.data());
+                    mpg_host_spmv(&A, x_true.data(), b.data());
+                }
+                print_norms();
+            }
+            std::cout << banner << std::endl;
+            if (j == 0) {
+                st = mpg_engine_create(&a, &eng, r.message, (int)sizeof r.message);
+            } else {
+                st = mpg_engine_rearm(eng, b.data(), nullptr, x_true.data(), 0);
+                if (st != 0) std::snprintf(r.message, sizeof r.message, "%s", mpg_engine_last_error(eng));
+            }
+            if (st != 0) break;
+            const auto t1 = std::chrono::steady_clock::now();
+            int done = 0;
+            while (!done && st == 0) {
+                const int ran = mpg_engine_run(eng, 1 << 20, &done);
+                if (ran < 0) {
+                    st = ran;
+                    std::snprintf(r.message, sizeof r.message, "%s", mpg_engine_last_error(eng));
+                }
+            }
+            if (st != 0) break;
+            mpg_engine_sync(eng);
+            const double gmres_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+            r = mpg_solve_result{};
+            st = mpg_engine_report(eng, &r);
+            if (st != 0) break;
+            std::cout << "  ilu took " << (float)r.setup_seconds << "s; gmres took " << (float)gmres_s << "s" << std::endl;
+            std::cout << "  resNorm = " << r.res_norm << "; errNorm = " << r.err_norm << std::endl;
+        }
+        mpg_engine_destroy(eng);
+    } else if (ngpus >= 1 && !(ngpus == 1 && a.engine != MPG_ENGINE_FUSED)) {
         std::vector<int32_t> devices((size_t)ngpus);
         for (int q = 0; q < ngpus; ++q) devices[(size_t)q] = a.device + q;
         std::cout << (a.mode == MPG_MODE_MIXED || a.mode == MPG_MODE_MIXED_HALF ? "Doing Mixed Precision test"

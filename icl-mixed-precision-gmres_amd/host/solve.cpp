@@ -233,6 +233,10 @@ int solve_surface(const mpg_solve_args& a, mpg_solve_result* r) {
 }  // namespace mpg
 
 extern "C" int mpg_solve(const mpg_solve_args* args, mpg_solve_result* result) {
+    return mpg_solve_from(args, nullptr, result);
+}
+
+extern "C" int mpg_solve_from(const mpg_solve_args* args, const double* x0, mpg_solve_result* result) {
     if (!args || !result) return MPG_ERR_ARG;
     result->status = MPG_RESULT_ERROR;
     result->message[0] = '\0';
@@ -249,6 +253,10 @@ extern "C" int mpg_solve(const mpg_solve_args* args, mpg_solve_result* result) {
             throw mpg::StatusError(MPG_ERR_UNSUPPORTED,
                                    "mpgmres: accum f32 runs on the fused engine only (the operator surface's "
                                    "kernels accumulate in fp64)");
+        if (x0 && args->engine != MPG_ENGINE_FUSED)
+            throw mpg::StatusError(MPG_ERR_UNSUPPORTED,
+                                   "mpgmres: an initial guess runs on the fused engine only (the operator surface's "
+                                   "drivers start from x0 = 0 as the reference's do)");
         mpg::set_quiet(!args->verbose);
         mpg_ctx_t ctx = nullptr;
         mpg::check(mpg_ctx_create(args->device, &ctx), "mpg_ctx_create");
@@ -256,7 +264,7 @@ extern "C" int mpg_solve(const mpg_solve_args* args, mpg_solve_result* result) {
         int st;
         {
             mpg::ScopedContext scope(ctx);
-            st = args->engine == MPG_ENGINE_FUSED ? mpg::solve_fused(*args, result)
+            st = args->engine == MPG_ENGINE_FUSED ? mpg::solve_fused(*args, result, x0)
                                                   : mpg::solve_surface(*args, result);
             mpg::check(mpg_ctx_sync(ctx), "final sync", ctx);
         }

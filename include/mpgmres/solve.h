@@ -5,6 +5,13 @@
  * x0 = 0, timer around the GMRES call only, then resNorm = ||b - A x|| with
  * the original fp64 A and errNorm = ||x - x_true||.
  *
+ * Beyond the reference (additions): mpg_solve_from starts from an initial
+ * guess, and a live fused engine takes further systems with the same matrix
+ * (mpg_engine_rearm: a new b, an initial guess, vectors in host or device
+ * memory; mpg_engine_x reads the iterate back) without repeating the set-up --
+ * the matrix copies, the preconditioner, the cycle policy and the captured
+ * cycle graph are kept.
+ *
  * The same argument/result structs are used by the HIP path
  * (libmpgmres_host.so: mpg_solve) and by the CPU oracle under oracle/
  * (liboracle.so: oracle_solve), so parity tests can run both on one input.
@@ -132,6 +139,12 @@ typedef struct {
 /* HIP path (libmpgmres_host.so). Returns 0 on success (result->status tells
  * converged/aborted), < 0 on error (result->message). */
 int mpg_solve(const mpg_solve_args* args, mpg_solve_result* result);
+/* mpg_solve from the initial guess x0 (host, n; an addition to the reference's set, whose drivers start from
+ * zeros): the iterate starts as x0 rounded once to the solve's outer type, and the first restart's true residual is
+ * b - A x0. x0 == NULL is mpg_solve. Fused engine only: with the operator-surface engine and a non-NULL x0 the
+ * call returns MPG_ERR_UNSUPPORTED and the message names the fused engine. The same bits as mpg_engine_rearm with
+ * that x0 on an engine created from `args`. */
+int mpg_solve_from(const mpg_solve_args* args, const double* x0, mpg_solve_result* result);
 
 /* ---- stepped access to the fused engine (benchmarks, multi-GPU ranks) ----
  * mpg_engine_create uploads the problem, builds the preconditioner, zeroes
@@ -143,8 +156,35 @@ int mpg_solve(const mpg_solve_args* args, mpg_solve_result* result);
 typedef struct mpg_engine* mpg_engine_t;
 int mpg_engine_create(const mpg_solve_args* args, mpg_engine_t* out, char* err, int errlen);
 int mpg_engine_run(mpg_engine_t e, int max_cycles, int* done);
-/* the error text of the last mpg_engine_run that failed ("" otherwise) */
+/* the error text of the last engine call that failed ("" otherwise) */
 const char* mpg_engine_last_error(mpg_engine_t e);
+/* ---- a sequence of systems on one engine (an addition to the reference's set) ----
+ * mpg_engine_rearm starts another solve with the engine's matrix: a new right-hand side b (NULL: keep the current
+ * one), an initial guess x0 (NULL: zeros) and a new x_true for errNorm (host, n; NULL: none -- it is copied, the
+ * caller's array may go after the call). b and x0 are fp64 arrays of n in host memory, or in the memory of the
+ * engine's device where `flags` says so (MPG_ARM_B_DEVICE, MPG_ARM_X0_DEVICE; the caller's own work on them must
+ * have completed). It runs the part of mpg_engine_create that depends on b and x -- the casts to the solve's types,
+ * ||b||, ||M^-1 b||, the first residual prologue -- and resets the solve's host state (history, counts, status, the
+ * convergence strategy, the breakdown report), so the solve that follows has the bits of a new engine created with
+ * these vectors. Nothing else is redone: the storage copies of A, the preconditioner, ||A||_F, the cycle policy and
+ * the captured cycle graph are kept, and no buffer moves. Allowed after a converged, aborted, broken-down or
+ * unfinished solve (nothing is in flight when mpg_engine_run returns). After it, mpg_engine_report reports the new
+ * solve only, and its setup_seconds is the duration of the re-arm.
+ * MPG_ERR_ARG: e is NULL (nothing is touched). MPG_ERR_UNSUPPORTED, the reason in mpg_engine_last_error: a
+ * row-partitioned engine (the norms and the halo of x0 would have to cross the ranks), or an engine that ran
+ * measurement launches (mpg_engine_time_*; mpg_engine_run's rule and text). */
+#define MPG_ARM_B_DEVICE 1
+#define MPG_ARM_X0_DEVICE 2
+int mpg_engine_rearm(mpg_engine_t e, const double* b, const double* x0, const double* x_true, int flags);
+/* rows [0, n) of the engine's iterate x widened to fp64 into dst (n entries; host memory, or the engine's device
+ * where dst_on_device != 0); synchronises the engine's stream before it returns. MPG_ERR_ARG: e or dst is NULL. */
+int mpg_engine_x(mpg_engine_t e, double* dst, int dst_on_device);
+/* solves armed on the engine so far, mpg_engine_create's included (>= 1); MPG_ERR_ARG: e is NULL */
+int mpg_engine_solves(mpg_engine_t e);
+/* cycle graphs the engine has captured so far: 1 once a solve has replayed the cycle, however many solves
+ * followed; 0 for an engine that runs eagerly or step by step (MPG_NO_GRAPH, the stepwise strategies);
+ * MPG_ERR_ARG: e is NULL */
+int mpg_engine_graph_captures(mpg_engine_t e);
 int mpg_engine_sync(mpg_engine_t e);
 int64_t mpg_engine_total_iters(mpg_engine_t e);
 /* The solve so far as mpg_solve reports it: status, counts, the per-cycle
