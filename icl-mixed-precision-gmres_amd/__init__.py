@@ -230,6 +230,10 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_x.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.mpg_engine_solves.argtypes = [C.c_void_p]
     lib.mpg_engine_graph_captures.argtypes = [C.c_void_p]
+    lib.mpg_engine_refresh_values.argtypes = [C.c_void_p, C.c_void_p, _I64, C.c_int]
+    lib.mpg_engine_refresh_seconds.argtypes = [C.c_void_p]
+    lib.mpg_engine_refresh_seconds.restype = C.c_double
+    lib.mpg_perturb_values.argtypes = [C.c_void_p, _I64, C.c_double, C.c_uint64, C.c_void_p]
 
 
 # (name, argtypes) for the kernel-level C-ABI, used by the per-kernel tests
@@ -283,6 +287,9 @@ _HIP_DECLS.update({
     "mpg_sell_create": ([_P, _P, _I32, _P, _I32, C.POINTER(_P)], C.c_int),
     "mpg_sell_shared_slices": ([_P], C.c_int64),
     "mpg_sell_destroy": ([_P], C.c_int),
+    "mpg_sell_refresh_values": ([_P, _P, _P, _I32, _P], C.c_int),
+    "mpg_sell_bytes": ([_P], C.c_int64),
+    "mpg_arnoldi_refresh_values": ([_P], C.c_int),
     "mpg_sell_layout": ([_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32)], C.c_int),
     "mpg_sell_spmv_f64": ([_P, _P, C.c_double, _P, C.c_double, _P], C.c_int),
     "mpg_sell_spmv_f32": ([_P, _P, C.c_float, _P, C.c_float, _P], C.c_int),
@@ -528,6 +535,18 @@ def rand_vect(n: int, seed: int = 42) -> np.ndarray:
     return out
 
 
+def perturb_values(A, eps: float, seed: int) -> np.ndarray:
+    """val * (1 + eps * u), u in [-1, 1) from the generators' counter-based
+    hash of (seed, index) (mpg_perturb_values): the values of the next matrix
+    of a sequence on one sparsity pattern (Engine.refresh; the CLI's
+    --vary-values). A: a Csr, or an fp64 array of values."""
+    val = np.ascontiguousarray(A.val if isinstance(A, Csr) else A, dtype=np.float64)
+    out = np.empty_like(val)
+    if host_lib().mpg_perturb_values(val.ctypes.data, val.size, eps, seed, out.ctypes.data):
+        raise ValueError("mpg_perturb_values failed")
+    return out
+
+
 def host_spmv(A: Csr, x: np.ndarray) -> np.ndarray:
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = np.empty(A.nrows, dtype=np.float64)
@@ -653,6 +672,7 @@ def run_solve(fn, args: SolveArgs, n: int, cycle_cap: int = 4096, step_cap: int 
 
 
 ARM_B_DEVICE, ARM_X0_DEVICE = 1, 2  # MPG_ARM_B_DEVICE, MPG_ARM_X0_DEVICE (solve.h)
+REFRESH_VAL_DEVICE = 1  # MPG_REFRESH_VAL_DEVICE
 
 
 def _is_tensor(v) -> bool:
@@ -993,16 +1013,48 @@ class Engine:
             raise RuntimeError(f"mpg_engine_rearm failed ({st}): {msg}")
         self._done = False
 
+    def refresh(self, values) -> None:
+        """New values of A on the sparsity pattern the engine was created
+        with (mpg_engine_refresh_values): nnz fp64 values in CSR order, a
+        NumPy array or an fp64 torch tensor on the engine's device (read in
+        place, left unmodified). Everything that reads the values is redone
+        as a new engine does it; the CSR analysis, the storage layouts, the
+        workspace, the cycle policy and -- where its launch arguments did not
+        change -- the captured graph are kept. The engine is left unarmed:
+        rearm() (or solve(...) with a vector) must follow before run().
+        ValueError: values of the wrong type, length or device, before
+        anything is touched. RuntimeError with the status: a row-partitioned
+        or measured engine, mixed-half values the engine's kernels cannot
+        take (the engine keeps its matrix), or a failure that leaves the
+        engine dead."""
+        nnz = int(self._args.nnz)
+        ptr, on_dev, keep = _arm_vector(values, nnz, self._args.device, "values")
+        st = self._lib.mpg_engine_refresh_values(self._h, ptr, nnz, REFRESH_VAL_DEVICE if on_dev else 0)
+        del keep
+        if st:
+            msg = self._lib.mpg_engine_last_error(self._h).decode(errors="replace")
+            raise RuntimeError(f"mpg_engine_refresh_values failed ({st}): {msg}")
+        self._done = False
+
+    @property
+    def refresh_seconds(self) -> float:
+        """Duration of the last refresh (mpg_engine_refresh_seconds); 0 before the first."""
+        return float(self._lib.mpg_engine_refresh_seconds(self._h))
+
     def solve(self, b=None, x0=None, x_true=None, max_cycles: Optional[int] = None, cycle_cap: int = 4096,
-              step_cap: int = 1 << 17) -> Result:
+              step_cap: int = 1 << 17, values=None) -> Result:
         """One solve on the live engine: re-arm if any of b, x0, x_true is
         given (rearm), run until done or for at most max_cycles restart
         cycles, and report. Without arguments it finishes the solve the engine
         is armed with (the constructor's, or the last rearm's); a finished
-        solve is only reported again. gmres_seconds: the run, timed here."""
+        solve is only reported again. values: new values of A first
+        (refresh), then the re-arm (b None keeps the right-hand side), then
+        the run. gmres_seconds: the run, timed here."""
         import time
 
-        if b is not None or x0 is not None or x_true is not None:
+        if values is not None:
+            self.refresh(values)
+        if values is not None or b is not None or x0 is not None or x_true is not None:
             self.rearm(b, x0, x_true)
         t0 = time.perf_counter()
         left = max_cycles

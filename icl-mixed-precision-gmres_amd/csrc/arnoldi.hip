@@ -224,6 +224,21 @@ int mpg_arnoldi_spmv_layout(mpg_arnoldi_t a, int32_t* format, int32_t* vec_width
     return MPG_OK;
 }
 
+int mpg_arnoldi_refresh_values(mpg_arnoldi_t a) {
+    if (!a) return MPG_ERR_ARG;
+    const mpg_arnoldi_desc& d = a->d;
+    if (a->node.nblk > 0) {
+        if (int st = node_refresh(a->ctx, d.A, d.inner_val, d.val_inner, a->node)) return st;
+        if (a->node_res == &a->node_outer) return node_refresh(a->ctx, d.A, MPG_F64, d.val_outer, a->node_outer);
+        return MPG_OK;
+    }
+    if (a->sell.nslices == 0) return MPG_OK;  // CSR row blocks read d.val_inner / d.val_outer themselves
+    if (int st = sell_refresh(a->ctx, d.A, d.inner_val, d.val_inner, a->sell)) return st;
+    if (!a->outer_is_inner && a->sell_outer.nslices > 0)
+        return sell_refresh(a->ctx, d.A, d.outer_type, d.val_outer, a->sell_outer);
+    return MPG_OK;
+}
+
 int mpg_arnoldi_destroy(mpg_arnoldi_t a) {
     if (!a) return MPG_OK;
     if (a->ctx) (void)hipStreamSynchronize(a->ctx->stream);

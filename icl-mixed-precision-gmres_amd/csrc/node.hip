@@ -238,6 +238,32 @@ int node_tpw_default() {
     return e && *e ? std::atoi(e) : 2;
 }
 
+// the records of S from `val` (S.vtype) over S.bptr: exact blocks one wave per
+// node row, padded ones one thread per node row (the build's and node_refresh's one launch)
+static void node_fill(const mpg_csr* A, const void* val, const NodeCopy& S, hipStream_t stream) {
+    const int nn = S.nn;
+    auto* o = static_cast<uint32_t*>(S.recs);
+    auto go = [&](auto vi) {
+        using VI = decltype(vi);
+        if (S.pad_fill)
+            k_node_fill_padded<VI><<<(nn + kBlock - 1) / kBlock, kBlock, 0, stream>>>(
+                nn, A->rowptr, A->col, static_cast<const VI*>(val), S.bptr, o);
+        else
+            k_node_fill<VI><<<(int)(((int64_t)nn * kWave + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
+                nn, A->rowptr, A->col, static_cast<const VI*>(val), S.bptr, o);
+    };
+    if (S.vtype == MPG_F64) go(double());
+    else if (S.vtype == MPG_F32) go(float());
+    else go(half_v());
+}
+
+int node_refresh(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, NodeCopy& S) {
+    if (!ctx || !A || !val || S.nblk == 0 || vtype != S.vtype || A->rows != S.nn * kNodeDof) return MPG_ERR_ARG;
+    node_fill(A, val, S, ctx->stream);
+    MPG_LAUNCH_CHECK(ctx);
+    return MPG_OK;
+}
+
 int node_build(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, bool required, NodeCopy& S,
                int64_t alt_bytes) {
     S = NodeCopy{};
@@ -313,30 +339,9 @@ int node_build(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, bool 
               hipMemcpyAsync(S.bptr, bptr.data(), bptr.size() * 4, hipMemcpyHostToDevice, stream) == hipSuccess &&
               hipMemcpyAsync(S.tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, stream) == hipSuccess;
     S.padded = padded ? nb * kNodeDof * kNodeDof - A->nnz : 0;
-    if (ok && padded) {
-        auto* o = static_cast<uint32_t*>(S.recs);
-        const int g = (nn + kBlock - 1) / kBlock;
-        if (vtype == MPG_F64)
-            k_node_fill_padded<double><<<g, kBlock, 0, stream>>>(nn, A->rowptr, A->col,
-                                                                 static_cast<const double*>(val), S.bptr, o);
-        else if (vtype == MPG_F32)
-            k_node_fill_padded<float><<<g, kBlock, 0, stream>>>(nn, A->rowptr, A->col,
-                                                                static_cast<const float*>(val), S.bptr, o);
-        else
-            k_node_fill_padded<half_v><<<g, kBlock, 0, stream>>>(nn, A->rowptr, A->col,
-                                                                 static_cast<const half_v*>(val), S.bptr, o);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-    } else if (ok) {
-        auto* o = static_cast<uint32_t*>(S.recs);
-        if (vtype == MPG_F64)
-            k_node_fill<double><<<grid, kBlock, 0, stream>>>(nn, A->rowptr, A->col, static_cast<const double*>(val),
-                                                             S.bptr, o);
-        else if (vtype == MPG_F32)
-            k_node_fill<float><<<grid, kBlock, 0, stream>>>(nn, A->rowptr, A->col, static_cast<const float*>(val),
-                                                            S.bptr, o);
-        else
-            k_node_fill<half_v><<<grid, kBlock, 0, stream>>>(nn, A->rowptr, A->col, static_cast<const half_v*>(val),
-                                                             S.bptr, o);
+    S.pad_fill = padded;
+    if (ok) {
+        node_fill(A, val, S, stream);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
     }
     if (!ok) {

@@ -45,6 +45,7 @@ struct NodeCopy {
     int rec = 0;           // record bytes
     bool xcd = false;      // scattered columns: tiles in XCD order (node_xcd)
     int64_t padded = 0;    // zero slots of padded node blocks (0: exact blocks)
+    bool pad_fill = false; // the records were filled as padded blocks (k_node_fill_padded; node_refresh fills alike)
     int32_t* bptr = nullptr;   // nn + 1 block starts
     int32_t* tiles = nullptr;  // ntiles + 1 node-row starts, then ntiles + 1 block starts (tb0)
     void* recs = nullptr;      // nblk records
@@ -58,6 +59,10 @@ struct NodeCopy {
 int node_build(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, bool required, NodeCopy& S,
                int64_t alt_bytes = -1);
 void node_free(NodeCopy& S);
+// New values on the unchanged pattern: the records filled again from `val`
+// (vtype == S.vtype) by the kernel that filled them at the build, over the
+// kept block starts. One launch on the context's stream, no synchronisation.
+int node_refresh(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, NodeCopy& S);
 // bytes the Arnoldi SpMV streams from the copy: records, block and tile starts
 int64_t node_bytes(const NodeCopy& S);
 

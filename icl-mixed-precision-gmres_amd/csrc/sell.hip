@@ -125,6 +125,44 @@ __global__ void k_sell_fill(int n, int nslices, const int32_t* __restrict__ rowp
     }
 }
 
+// k_sell_fill's values alone, on a built copy whose columns may since have
+// been compacted (sell_share_columns, implicit slices): the value array keeps
+// the off[] layout, so the same lane writes the same places, S(0) into the
+// pads (rows >= n of the tail slice are all pads)
+template <class S, int W>
+__global__ __launch_bounds__(kBlock) void k_sell_refill(int n, int nslices, const int32_t* __restrict__ rowptr,
+                                                        const S* __restrict__ val, const int64_t* __restrict__ off,
+                                                        S* __restrict__ sval, const int32_t* __restrict__ rows) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = (int)(t / kWave), lane = (int)(t % kWave);
+    if (s >= nslices) return;
+    const int r = rows ? rows[s * kWave + lane] : s * kWave + lane;
+    const int64_t o = off[s];
+    const int width = (int)((off[s + 1] - o) / kWave);
+    const int b = r < n ? rowptr[r] : 0, len = r < n ? rowptr[r + 1] - b : 0;
+    for (int j = 0; j < width; ++j) {
+        const int64_t pos = o + (int64_t)(j / W) * kWave * W + lane * W + (j % W);
+        sval[pos] = j < len ? val[b + j] : S(0);
+    }
+}
+
+// the CSR-summed slices' values again (S.xval): lane l of wave e copies row
+// 64 xslice[e] + l of `val` to where xrp says the build put it
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_sell_xval_refill(int n, int64_t nexc, const int32_t* __restrict__ rowptr,
+                                                             const S* __restrict__ val,
+                                                             const int32_t* __restrict__ xslice,
+                                                             const int32_t* __restrict__ xrp, S* __restrict__ xval) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = t / kWave;
+    const int lane = (int)(t % kWave);
+    if (e >= nexc) return;
+    const int r = xslice[e] * kWave + lane;
+    if (r >= n) return;
+    const int dst = xrp[e * kWave + lane], len = xrp[e * kWave + lane + 1] - dst, src = rowptr[r];
+    for (int j = 0; j < len; ++j) xval[dst + j] = val[src + j];
+}
+
 // Shared column blocks: slices whose stored column blocks are identical
 // (2-byte forms: offsets relative to the slice, so every interior slice of
 // a stencil with the same boundary pattern has the same block) keep one copy.
@@ -675,9 +713,11 @@ int sell_build(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, int f
         // adjacent flagged slices in one copy each
         std::vector<int32_t> xrp_h((size_t)S.nexc * kWave + 1, 0);
         std::vector<std::pair<int64_t, int64_t>> runs;  // (first entry, entry count) per run of flagged slices
+        std::vector<int32_t> xslice_h;  // the flagged slices, in order (sell_refresh)
         int64_t e = 0, at = 0;
         for (int s2 = 0; s2 < ns; ++s2) {
             if (spat_h[s2] > -2) continue;
+            xslice_h.push_back(s2);
             for (int l = 0; l < kWave; ++l) {
                 const int r = s2 * kWave + l;
                 const int64_t len = r < n ? (int64_t)rp[r + 1] - rp[r] : 0;
@@ -691,9 +731,12 @@ int sell_build(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, int f
         }
         if (hipMalloc((void**)&S.xrp, xrp_h.size() * 4) != hipSuccess ||
             hipMalloc((void**)&S.xcol, (size_t)at * 4 + 256) != hipSuccess ||
-            hipMalloc(&S.xval, (size_t)at * vsize + 256) != hipSuccess) {
+            hipMalloc(&S.xval, (size_t)at * vsize + 256) != hipSuccess ||
+            hipMalloc((void**)&S.xslice, xslice_h.size() * 4) != hipSuccess) {
             st = MPG_ERR_ALLOC;
-        } else if (hipMemcpyAsync(S.xrp, xrp_h.data(), xrp_h.size() * 4, hipMemcpyHostToDevice, stream) != hipSuccess) {
+        } else if (hipMemcpyAsync(S.xrp, xrp_h.data(), xrp_h.size() * 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                   hipMemcpyAsync(S.xslice, xslice_h.data(), xslice_h.size() * 4, hipMemcpyHostToDevice, stream) !=
+                       hipSuccess) {
             st = MPG_ERR_HIP;
         } else {
             int64_t dst = 0;
@@ -835,6 +878,32 @@ int sell_share_columns(SellCopy& S, const std::vector<int64_t>& off, const std::
     return cleanup(MPG_OK);
 }
 
+int sell_refresh(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, SellCopy& S) {
+    if (!ctx || !A || !val || S.nslices == 0 || vtype != S.vtype || A->rows != S.n) return MPG_ERR_ARG;
+    if (S.nexc > 0 && !S.xslice) return MPG_ERR_ARG;
+    const int grid = (int)(((int64_t)S.nslices * kWave + kBlock - 1) / kBlock);
+    const int xgrid = (int)((S.nexc * kWave + kBlock - 1) / kBlock);
+    hipStream_t stream = ctx->stream;
+    int st = with_store(vtype, [&](auto sv) {
+        using St = decltype(sv);
+        auto go = [&](auto wc) {
+            k_sell_refill<St, decltype(wc)::value><<<grid, kBlock, 0, stream>>>(
+                S.n, S.nslices, A->rowptr, static_cast<const St*>(val), S.off, static_cast<St*>(S.val), S.rows);
+        };
+        if (S.W == 4) go(std::integral_constant<int, 4>());
+        else if (S.W == 2) go(std::integral_constant<int, 2>());
+        else if (S.W == 1) go(std::integral_constant<int, 1>());
+        else return (int)MPG_ERR_UNSUPPORTED;
+        if (S.nexc > 0)
+            k_sell_xval_refill<St><<<xgrid, kBlock, 0, stream>>>(S.n, S.nexc, A->rowptr, static_cast<const St*>(val),
+                                                                 S.xslice, S.xrp, static_cast<St*>(S.xval));
+        return (int)MPG_OK;
+    });
+    if (st) return st;
+    MPG_LAUNCH_CHECK(ctx);
+    return MPG_OK;
+}
+
 int64_t sell_matrix_bytes(const SellCopy& S) {
     if (S.nslices == 0) return 0;
     const int64_t vbytes = S.vtype == MPG_F64 ? 8 : S.vtype == MPG_F32 ? 4 : 2;
@@ -859,6 +928,7 @@ void sell_free(SellCopy& S) {
     if (S.xrp) (void)hipFree(S.xrp);
     if (S.xcol) (void)hipFree(S.xcol);
     if (S.xval) (void)hipFree(S.xval);
+    if (S.xslice) (void)hipFree(S.xslice);
     if (S.coff) (void)hipFree(S.coff);
     if (S.rows) (void)hipFree(S.rows);
     S = SellCopy{};
@@ -937,6 +1007,11 @@ int mpg_sell_create(mpg_ctx_t ctx, mpg_csr_t A, int32_t vtype, const void* vals,
     }
     *out = h;
     return MPG_OK;
+}
+
+int mpg_sell_refresh_values(mpg_ctx_t ctx, mpg_sell_t S, mpg_csr_t A, int32_t vtype, const void* vals) {
+    if (!ctx || !S || !A || !vals || A->rows != S->S.n || A->cols != S->cols || vtype != S->S.vtype) return MPG_ERR_ARG;
+    return sell_refresh(ctx, A, vtype, vals, S->S);
 }
 
 int mpg_sell_destroy(mpg_sell_t A) {

@@ -326,6 +326,7 @@ struct SellCopy {
     int32_t* xrp = nullptr;    // their rows as a CSR owned by the copy: 64 nexc + 1 row starts
     int32_t* xcol = nullptr;   //   (row 64 e + lane of flagged slice e; rows past n are empty),
     void* xval = nullptr;      //   columns and values (the stored value type) in CSR order
+    int32_t* xslice = nullptr; //   the flagged slices' numbers, nexc of them (sell_refresh re-copies their values)
     int64_t nimp = 0;          // implicit slices
     int64_t imp_slots = 0;     // their slots (their columns are not read)
     int64_t npat = 0;          // pattern entries
@@ -358,6 +359,12 @@ namespace mpg {
 // entries), 1 never, 2 always. Synchronises the context's stream.
 int sell_build(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, int format, SellCopy& S);
 void sell_free(SellCopy& S);
+// New values on the unchanged pattern (mpg_sell_refresh_values): `val` (vtype
+// == S.vtype, CSR order, device) into S.val at the places the build filled,
+// zeros into the pads, the CSR-summed slices' rows into S.xval. Values only:
+// no column, base or pattern is read or written and no address moves. Two
+// launches at most on the context's stream, no host synchronisation.
+int sell_refresh(mpg_ctx* ctx, const mpg_csr* A, int vtype, const void* val, SellCopy& S);
 // matrix bytes one SpMV over the copy reads (mpg_sell_bytes)
 int64_t sell_matrix_bytes(const SellCopy& S);
 

@@ -142,6 +142,7 @@ struct FusedEngine::Impl {
     DevMem rowptr, col, val64, val_outer_own, val_inner_own, diag, b, x, tmp_t, tmp_p, scal;
     DevMem row_exp;                 // mixed-half: per-row exponents of the scaled fp16 values
     int64_t half_stats[4] = {0, 0, 0, 0};
+    bool half_scaled = false;       // ... and the workspace runs the scaled kernels (chosen at create, kept for good)
     const void* val_outer = nullptr;
     const void* val_inner = nullptr;
     mpg_csr_t csr = nullptr;
@@ -457,57 +458,211 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     check(mpg_csr_create(ctx, I.n, I.n_ext, I.nnz, a.rowptr, I.rowptr.as<int32_t>(), I.col.as<int32_t>(), &I.csr),
           "mpg_csr_create", ctx);
 
+    // everything that reads the values (load_values: a values refresh comes through it again)
+    I.scal = DevMem(ctx, 64);
+    I.tmp_t = DevMem(ctx, (size_t)I.n * dsize(I.ty.T) + 64);
+    if (I.ty.P != I.ty.T) I.tmp_p = DevMem(ctx, (size_t)I.n * dsize(I.ty.P) + 64);
+    load_values(a.val, false);
+    const ModeTypes& ty = I.ty;
+
+    // b and x (outer type, x with halo tail), the work vectors of the arm
+    // (tmp_t: T(b), tmp_p: typesafe_apply's P copy, above); their values are arm()'s
+    I.b = DevMem(ctx, (size_t)I.n * dsize(ty.X) + 8);
+    if (ty.X != MPG_F64) I.stage64 = DevMem(ctx, (size_t)I.n * 8 + 8);
+    I.x = DevMem(ctx, (size_t)(I.front + I.n_ext) * dsize(ty.X) + 64);
+    I.xp = static_cast<char*>(I.x.p) + (size_t)I.front * dsize(ty.X);
+
+    mpg_arnoldi_desc d{};
+    d.n = I.n;
+    d.n_ext = I.n_ext;
+    d.m = I.m;
+    d.orth = I.orth;
+    d.vec_type = ty.T;
+    d.outer_type = ty.X;
+    d.prec_type = ty.P;
+    d.inner_val = ty.VI;
+    d.jacobi = I.jacobi_inside();
+    d.A = I.csr;
+    d.val_outer = I.val_outer;
+    d.val_inner = I.val_inner;
+    // (the sweeps' diagonal rides in the descriptor with jacobi = 0: the phase
+    // kernels apply no preconditioner, mpg_arnoldi_neumann_apply reads it)
+    d.diag = d.jacobi || neumann ? I.diag.p : nullptr;
+    d.b = I.b.p;
+    d.x = I.xp;
+    d.spmv_format = a.spmv_format;
+    // a compressed basis: auto picks among CSR row blocks and the SELL copy
+    // (no node blocks); the emulated one is built for the CSR kernel
+    if (I.basis != MPG_BASIS_F32 && a.spmv_format == 0) d.spmv_format = I.basis == MPG_BASIS_F16EMU ? 1 : 4;
+    d.n_front = n_front;
+    {
+        const char* benv = std::getenv("MPG_BJACOBI_FUSE");
+        if (I.bj_bs && benv && *benv == '1') {
+            d.block_dinv = I.bj_dinv.p;
+            d.prec_block = I.bj_bs;
+        }
+    }
+    // rows all in range: the unscaled kernels (no exponent loads, same bits)
+    I.half_scaled = I.half_stats[0] > 0;
+    d.inner_row_exp = I.half_scaled ? I.row_exp.as<int8_t>() : nullptr;
+    check(mpg_arnoldi_create(ctx, &d, &I.arn), "mpg_arnoldi_create", ctx);
+    I.bj_fused_step = mpg_arnoldi_prec_fused(I.arn, 0) == 1;
+    I.bj_fused_prologue = mpg_arnoldi_prec_fused(I.arn, 1) == 1;
+    // fp32 Arnoldi: the reference's fp32 accumulation class on request (arnoldi.h)
+    if (a.accum) check(mpg_arnoldi_set_accum(I.arn, MPG_ACCUM_F32), "mpg_arnoldi_set_accum", ctx);
+    if (I.basis != MPG_BASIS_F32) check(mpg_arnoldi_set_basis(I.arn, I.basis), "mpg_arnoldi_set_basis", ctx);
+    // (the GMRES polynomial: for the asked degree, so that the root count of refreshed values fits)
+    const int nm_cap = I.poly ? a.jacobi_steps : I.nm_steps;
+    if (nm_cap >= 2) I.nm_work0 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
+    if (nm_cap >= 3) I.nm_work1 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
+    // ranks all-reduce per-workgroup partials in place: same count on every rank
+    // (MPG_UNIFORM_GROUPS=1 gives one GPU the ranks' partial counts: a P = 1
+    // RCCL solve then has the single-GPU solve's bits, tests/test_dist_gpu.py)
+    const char* uenv = std::getenv("MPG_UNIFORM_GROUPS");
+    if (comm || (uenv && *uenv == '1')) check(mpg_arnoldi_uniform_groups(I.arn), "uniform groups", ctx);
+    I.report_len = mpg_arnoldi_report_len(I.arn);
+    for (double*& r : I.rep) hipck(hipHostMalloc((void**)&r, (size_t)I.report_len * sizeof(double), 0), "hipHostMalloc");
+    I.report_host = I.rep[0];
+    for (hipEvent_t& e : I.report_ev) hipck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "event");
+
+    if (I.orthloss) {
+        const size_t mm = (size_t)a.rlen;
+        I.loss_S = DevMem(ctx, (size_t)(mm + 1) * (mm + 1) * dsize(ty.T));
+        I.loss_u = DevMem(ctx, (size_t)(mm + 2) * dsize(ty.T));
+    }
+    breakdown.stop = a.stop_on_breakdown != 0;
+
+    I.resolve_policy();
+    if (I.pol.pipeline) I.x_snap = DevMem(ctx, I.x.bytes);
+    if (I.pol.pipeline && tail_fold())
+        check(mpg_arnoldi_set_x_snapshot(I.arn, static_cast<char*>(I.x_snap.p) + (size_t)I.front * dsize(I.ty.X)),
+              "x snapshot", ctx);
+    arm(a.b, x0, a.x_true, 0);
+    check(mpg_ctx_sync(ctx), "sync", ctx);
+    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
+    start();
+}
+
+namespace {
+const char* const kMeasuredText =
+    "the engine ran measurement launches (mpg_engine_time_*), which change its Krylov basis, "
+    "Hessenberg column and iterate; create a new engine to continue a solve";
+}
+
+// Everything the set-up derives from the values of A, from fp64 values in CSR
+// order (host memory, or the engine's device): the fp64 copy, the residual
+// and the Arnoldi matrix in their types, Jacobi's diagonal, the Chebyshev
+// interval, the GMRES-polynomial roots, the block-Jacobi inverses, the ILU
+// factors and ||A||_F. The constructor and refresh_values() both come through
+// here, so a refreshed engine runs a new engine's launches on a new engine's
+// numbers. On a live engine (the workspace exists) no buffer moves, the
+// workspace's storage copies are refilled (mpg_arnoldi_refresh_values) and a
+// captured cycle whose launch arguments changed is released. It reads none of
+// args' pointers: they are the caller's of create time and may be gone.
+void FusedEngine::load_values(const double* val, bool on_device) {
+    Impl& I = *p_;
+    const mpg_ctx_t ctx = I.ctx;
+    const mpg_solve_args& a = I.args;  // (its scalars only)
+    const ModeTypes& ty = I.ty;
+    Comm* const comm = I.comm;
+    const size_t nz = (size_t)I.nnz, nz1 = std::max<size_t>(nz, 1);
+    const bool live = I.arn != nullptr;
+    const bool ilu = a.prec == MPG_PREC_ILU || a.prec == MPG_PREC_ILU_JACOBI;
+    const bool neumann = a.prec == MPG_PREC_NEUMANN || I.cheb || I.poly;
+    auto need = [&](DevMem& m, size_t bytes) {
+        if (!m.p) m = DevMem(ctx, bytes);
+    };
+    const bool rounded_outer = a.mode != MPG_MODE_MIXED && a.mode != MPG_MODE_MIXED_HALF;
+    const bool half = !rounded_outer && ty.VI == MPG_F16;
+    const bool scale = a.half_unscaled == 0;
+
+    // A live mixed-half engine chose scaled or unscaled kernels when it was
+    // created: the fp16 conversion of the new values goes into scratch first,
+    // and values the engine's kernels cannot take are refused with the old
+    // matrix untouched
+    DevMem staged, half_new, exp_new;
+    int64_t stats_new[4] = {0, 0, 0, 0};
+    if (live && half) {
+        if (!on_device) {
+            staged = DevMem(ctx, nz1 * 8);
+            if (nz) check(mpg_memcpy_h2d(ctx, staged.p, val, nz * 8), "h2d", ctx);
+            val = staged.as<double>();
+            on_device = true;
+        }
+        half_new = DevMem(ctx, nz1 * 2);
+        if (scale) exp_new = DevMem(ctx, (size_t)I.n + 64);
+        const int st = mpg_csr_half_values(ctx, I.csr, val, scale ? 1 : 0, half_new.as<uint16_t>(),
+                                           scale ? exp_new.as<int8_t>() : nullptr, stats_new);
+        if (st == MPG_ERR_RANGE)
+            throw StatusError(MPG_ERR_RANGE,
+                              "mixed-half: the new values do not fit the fp16 Arnoldi copy (" +
+                                  std::to_string(stats_new[2]) + " entries overflow, " + std::to_string(stats_new[1]) +
+                                  " round to 0" + (scale ? "" : " under half_unscaled") +
+                                  "); the engine keeps its matrix");
+        check(st, "fp16 Arnoldi values", ctx);
+        if (!I.half_scaled && stats_new[0] > 0)
+            throw StatusError(MPG_ERR_UNSUPPORTED,
+                              "mixed-half: " + std::to_string(stats_new[0]) +
+                                  " rows of the new values need row scaling, and this engine was created on values "
+                                  "that needed none, with the unscaled kernels; the engine keeps its matrix -- create "
+                                  "a new engine for these values");
+    }
+    values_dirty_ = live;  // from here on a failure leaves a live engine without a consistent matrix
+
     // values: the original fp64 A, the residual matrix (outer type) and the
     // Arnoldi matrix (inner type) — gmres_perf_test.cpp:66 (baseline solves with
     // double(float(A))) and :136 (mixed: fp64 residual, fp32 Arnoldi)
-    I.val64 = DevMem(ctx, std::max<size_t>(nz, 1) * 8);
-    if (nz) check(mpg_memcpy_h2d(ctx, I.val64.p, a.val, nz * 8), "h2d", ctx);
-    const ModeTypes& ty = I.ty;
-    const bool rounded_outer = a.mode != MPG_MODE_MIXED && a.mode != MPG_MODE_MIXED_HALF;
+    need(I.val64, nz1 * 8);
+    if (nz && on_device) check(mpg_memcpy_d2d(ctx, I.val64.p, val, nz * 8), "d2d", ctx);
+    else if (nz) check(mpg_memcpy_h2d(ctx, I.val64.p, val, nz * 8), "h2d", ctx);
     if (rounded_outer) {
-        DevMem f32(ctx, std::max<size_t>(nz, 1) * 4);
-        I.cast(I.val64.p, MPG_F64, f32.p, MPG_F32, (int64_t)nz);
         if (ty.X == MPG_F64) {
-            I.val_outer_own = DevMem(ctx, std::max<size_t>(nz, 1) * 8);
+            DevMem f32(ctx, nz1 * 4);
+            I.cast(I.val64.p, MPG_F64, f32.p, MPG_F32, (int64_t)nz);
+            need(I.val_outer_own, nz1 * 8);
             I.cast(f32.p, MPG_F32, I.val_outer_own.p, MPG_F64, (int64_t)nz);
         } else {
-            I.val_outer_own = std::move(f32);
+            need(I.val_outer_own, nz1 * 4);
+            I.cast(I.val64.p, MPG_F64, I.val_outer_own.p, MPG_F32, (int64_t)nz);
         }
         I.val_outer = I.val_outer_own.p;
         I.val_inner = I.val_outer;  // the same matrix drives the Arnoldi cycle
     } else {
         I.val_outer = I.val64.p;
-        I.val_inner_own = DevMem(ctx, std::max<size_t>(nz, 1) * dsize(ty.VI));
-        if (ty.VI == MPG_F16) {
+        need(I.val_inner_own, nz1 * dsize(ty.VI));
+        if (half && live) {
+            if (nz) check(mpg_memcpy_d2d(ctx, I.val_inner_own.p, half_new.p, nz * 2), "d2d", ctx);
+            // (a scaled engine takes any exponents: all zero gives the unscaled bits)
+            if (I.half_scaled) check(mpg_memcpy_d2d(ctx, I.row_exp.p, exp_new.p, (size_t)I.n), "d2d", ctx);
+            std::copy(stats_new, stats_new + 4, I.half_stats);
+        } else if (half) {
             // fp16 values, scaled per row by powers of two where a row's
             // magnitude falls outside fp16's range (mpg_csr_half_values);
             // with a.half_unscaled such a matrix fails here (MPG_ERR_RANGE)
-            const bool scale = a.half_unscaled == 0;
             if (scale) I.row_exp = DevMem(ctx, (size_t)I.n + 64);
             check(mpg_csr_half_values(ctx, I.csr, I.val64.as<double>(), scale ? 1 : 0,
                                       I.val_inner_own.as<uint16_t>(), scale ? I.row_exp.as<int8_t>() : nullptr,
                                       I.half_stats),
                   "fp16 Arnoldi values", ctx);
-            // a row whose own range exceeds fp16's (~2^39 below its largest
-            // entry) loses its smallest entries to 0 even when scaled: not an
-            // error (the plain cast's MPG_ERR_RANGE case), but said
-            if (I.half_stats[1] > 0 && a.verbose)
-                std::fprintf(stderr,
-                             "mpgmres: mixed-half: %lld nonzero entries rounded to 0 in the fp16 Arnoldi copy "
-                             "(rows spanning more than fp16's range; %lld rows scaled)\n",
-                             (long long)I.half_stats[1], (long long)I.half_stats[0]);
         } else {
             I.cast(I.val64.p, MPG_F64, I.val_inner_own.p, ty.VI, (int64_t)nz);
         }
+        // a row whose own range exceeds fp16's (~2^39 below its largest
+        // entry) loses its smallest entries to 0 even when scaled: not an
+        // error (the plain cast's MPG_ERR_RANGE case), but said
+        if (half && I.half_stats[1] > 0 && a.verbose)
+            std::fprintf(stderr,
+                         "mpgmres: mixed-half: %lld nonzero entries rounded to 0 in the fp16 Arnoldi copy "
+                         "(rows spanning more than fp16's range; %lld rows scaled)\n",
+                         (long long)I.half_stats[1], (long long)I.half_stats[0]);
         I.val_inner = I.val_inner_own.p;
     }
 
     // Jacobi<P>(A): fp64 original A for P = double (baseline), else the A
     // converted to float (types.hpp:393-431 on SparseMatrix<P>)
     // (max row sum all-reduced across ranks: ||A||_inf of the whole matrix)
-    I.scal = DevMem(ctx, 64);
     if (a.prec == MPG_PREC_JACOBI || neumann) {
-        I.diag = DevMem(ctx, (size_t)I.n * dsize(ty.P) + 16);
+        need(I.diag, (size_t)I.n * dsize(ty.P) + 16);
         double* rowmax = I.scal.as<double>() + 4;
         if (ty.P == MPG_F64) {
             check(mpg_jacobi_rowmax_f64(ctx, I.csr, I.val64.as<double>(), rowmax), "jacobi", ctx);
@@ -545,13 +700,19 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
                                                       I.diag.as<double>(), I.n, a.jacobi_steps)
                            : gmres_poly_setup<float>(ctx, I.csr, static_cast<const float*>(I.val_inner),
                                                      I.diag.as<float>(), I.n, a.jacobi_steps);
+        // (a refresh may change the count, always >= 1. The cycle policy reads
+        // nm_steps only as "a preconditioner launch sits between the phase
+        // kernels" -- sep_prec* in resolve_policy, true for every count -- and
+        // jacobi_inside() is false under poly whatever nm_asked says, so the
+        // plan made at create holds; the count itself is an argument of
+        // apply_neumann's launches, which the re-captured graph takes anew)
         I.nm_asked = I.nm_steps = I.poly_roots.count;
     }
 
     // block Jacobi in the preconditioner precision, from the matrix Jacobi<P>
     // takes above: the fp64 A for P = double, else its fp32 copy
     if (I.bj_bs) {
-        I.bj_dinv = DevMem(ctx, (size_t)I.n * I.bj_bs * dsize(ty.P) + 16);
+        need(I.bj_dinv, (size_t)I.n * I.bj_bs * dsize(ty.P) + 16);
         int st;
         if (ty.P == MPG_F64) {
             st = mpg_bjacobi_setup_f64(ctx, I.csr, I.val64.as<double>(), I.bj_bs, I.bj_dinv.as<double>(), nullptr);
@@ -564,16 +725,16 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     }
 
     // ILU(0) of the fp64 A in the preconditioner precision (gmres_perf_test.cpp:70-79, 140-149)
+    // (new values: the factor object again, its level schedule included; no in-place refactorisation.
+    // A factorisation that fails returns its status here, inside the refresh; the fault word
+    // check_ilu_fault reads belongs to the triangular solves, which run from the re-arm on)
+    if (ilu && I.ilu) {
+        check(mpg_ctx_sync(ctx), "sync", ctx);
+        mpg_ilu_destroy(I.ilu);
+        I.ilu = nullptr;
+    }
     if (ilu) check(mpg_ilu0_create(ctx, I.csr, I.val64.as<double>(), ty.P == MPG_F64 ? 0 : 1, &I.ilu), "ilu0", ctx);
 
-    // b and x (outer type, x with halo tail), the work vectors of the arm
-    // (tmp_t: T(b), tmp_p: typesafe_apply's P copy); their values are arm()'s
-    I.b = DevMem(ctx, (size_t)I.n * dsize(ty.X) + 8);
-    if (ty.X != MPG_F64) I.stage64 = DevMem(ctx, (size_t)I.n * 8 + 8);
-    I.x = DevMem(ctx, (size_t)(I.front + I.n_ext) * dsize(ty.X) + 64);
-    I.xp = static_cast<char*>(I.x.p) + (size_t)I.front * dsize(ty.X);
-    I.tmp_t = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
-    if (ty.P != ty.T) I.tmp_p = DevMem(ctx, (size_t)I.n * dsize(ty.P) + 64);
     // ||A||_F of the matrix the driver was given (A_single in mixed mode)
     {
         const bool mixed = !rounded_outer;
@@ -589,72 +750,41 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
         a_norm = I.nrm2(av, at, (int64_t)nz);
     }
 
-    mpg_arnoldi_desc d{};
-    d.n = I.n;
-    d.n_ext = I.n_ext;
-    d.m = I.m;
-    d.orth = I.orth;
-    d.vec_type = ty.T;
-    d.outer_type = ty.X;
-    d.prec_type = ty.P;
-    d.inner_val = ty.VI;
-    d.jacobi = I.jacobi_inside();
-    d.A = I.csr;
-    d.val_outer = I.val_outer;
-    d.val_inner = I.val_inner;
-    // (the sweeps' diagonal rides in the descriptor with jacobi = 0: the phase
-    // kernels apply no preconditioner, mpg_arnoldi_neumann_apply reads it)
-    d.diag = d.jacobi || neumann ? I.diag.p : nullptr;
-    d.b = I.b.p;
-    d.x = I.xp;
-    d.spmv_format = a.spmv_format;
-    // a compressed basis: auto picks among CSR row blocks and the SELL copy
-    // (no node blocks); the emulated one is built for the CSR kernel
-    if (I.basis != MPG_BASIS_F32 && a.spmv_format == 0) d.spmv_format = I.basis == MPG_BASIS_F16EMU ? 1 : 4;
-    d.n_front = n_front;
-    {
-        const char* benv = std::getenv("MPG_BJACOBI_FUSE");
-        if (I.bj_bs && benv && *benv == '1') {
-            d.block_dinv = I.bj_dinv.p;
-            d.prec_block = I.bj_bs;
-        }
+    if (!live) return;
+    // the workspace's storage copies, from the arrays rewritten above (the
+    // descriptor's pointers are unchanged)
+    check(mpg_arnoldi_refresh_values(I.arn), "mpg_arnoldi_refresh_values", ctx);
+    // The captured cycle holds its launch arguments by value. Identity,
+    // Jacobi, block Jacobi and the Jacobi sweeps pass addresses only, which
+    // did not move: the graph stays. Chebyshev's theta / delta and the
+    // GMRES-polynomial roots are arguments by value, and the ILU factors are
+    // a new object: those cycles are captured again at the next solve.
+    if (I.cheb || I.poly || ilu) {
+        check(mpg_ctx_sync(ctx), "sync", ctx);
+        I.graph.reset();
     }
-    // rows all in range: the unscaled kernels (no exponent loads, same bits)
-    d.inner_row_exp = I.half_stats[0] > 0 ? I.row_exp.as<int8_t>() : nullptr;
-    check(mpg_arnoldi_create(ctx, &d, &I.arn), "mpg_arnoldi_create", ctx);
-    I.bj_fused_step = mpg_arnoldi_prec_fused(I.arn, 0) == 1;
-    I.bj_fused_prologue = mpg_arnoldi_prec_fused(I.arn, 1) == 1;
-    // fp32 Arnoldi: the reference's fp32 accumulation class on request (arnoldi.h)
-    if (a.accum) check(mpg_arnoldi_set_accum(I.arn, MPG_ACCUM_F32), "mpg_arnoldi_set_accum", ctx);
-    if (I.basis != MPG_BASIS_F32) check(mpg_arnoldi_set_basis(I.arn, I.basis), "mpg_arnoldi_set_basis", ctx);
-    if (I.nm_steps >= 2) I.nm_work0 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
-    if (I.nm_steps >= 3) I.nm_work1 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
-    // ranks all-reduce per-workgroup partials in place: same count on every rank
-    // (MPG_UNIFORM_GROUPS=1 gives one GPU the ranks' partial counts: a P = 1
-    // RCCL solve then has the single-GPU solve's bits, tests/test_dist_gpu.py)
-    const char* uenv = std::getenv("MPG_UNIFORM_GROUPS");
-    if (comm || (uenv && *uenv == '1')) check(mpg_arnoldi_uniform_groups(I.arn), "uniform groups", ctx);
-    I.report_len = mpg_arnoldi_report_len(I.arn);
-    for (double*& r : I.rep) hipck(hipHostMalloc((void**)&r, (size_t)I.report_len * sizeof(double), 0), "hipHostMalloc");
-    I.report_host = I.rep[0];
-    for (hipEvent_t& e : I.report_ev) hipck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "event");
+    values_dirty_ = false;
+}
 
-    if (I.orthloss) {
-        const size_t mm = (size_t)a.rlen;
-        I.loss_S = DevMem(ctx, (size_t)(mm + 1) * (mm + 1) * dsize(ty.T));
-        I.loss_u = DevMem(ctx, (size_t)(mm + 2) * dsize(ty.T));
-    }
-    breakdown.stop = a.stop_on_breakdown != 0;
-
-    I.resolve_policy();
-    if (I.pol.pipeline) I.x_snap = DevMem(ctx, I.x.bytes);
-    if (I.pol.pipeline && tail_fold())
-        check(mpg_arnoldi_set_x_snapshot(I.arn, static_cast<char*>(I.x_snap.p) + (size_t)I.front * dsize(I.ty.X)),
-              "x snapshot", ctx);
-    arm(a.b, x0, a.x_true, 0);
-    check(mpg_ctx_sync(ctx), "sync", ctx);
-    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
-    start();
+void FusedEngine::refresh_values(const double* val, int64_t nnz, int flags) {
+    Impl& I = *p_;
+    if (nnz != I.nnz || (nnz > 0 && !val))
+        throw StatusError(MPG_ERR_ARG, "mpg_engine_refresh_values: " + std::to_string(nnz) +
+                                           " values for an engine whose matrix stores " + std::to_string(I.nnz) +
+                                           " (the sparsity pattern is the engine's: one fp64 value per stored "
+                                           "entry, in CSR order)");
+    if (I.comm)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          "refreshing the values of a row-partitioned engine is not available: Jacobi's row "
+                          "maximum and ||A||_F would have to cross the ranks again, and the re-arm that must follow "
+                          "is not available there either");
+    if (measured) throw StatusError(MPG_ERR_UNSUPPORTED, kMeasuredText);
+    auto t0 = clk::now();
+    check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
+    load_values(val, (flags & MPG_REFRESH_VAL_DEVICE) != 0);
+    check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
+    armed_ = false;  // ||M^-1 b|| and the first residual belong to the old matrix: rearm() must follow
+    refresh_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 }
 
 // What a solve takes from b and x: the vectors in the outer type, the drivers'
@@ -747,18 +877,13 @@ void FusedEngine::arm(const double* b, const double* x0, const double* x_true, i
     } else conv_ = std::make_unique<RelPrecRes_Convergence<double, void>>(a.tol, a.rtol, mm, mr);
     conv_->total_iters = 0;
     ++solves_;
+    armed_ = true;
 }
 
 void FusedEngine::start() {
     prologue();
     read_report(4);
     if (p_->ilu) check_ilu_fault(p_->ilu);
-}
-
-namespace {
-const char* const kMeasuredText =
-    "the engine ran measurement launches (mpg_engine_time_*), which change its Krylov basis, "
-    "Hessenberg column and iterate; create a new engine to continue a solve";
 }
 
 void FusedEngine::rearm(const double* b, const double* x0, const double* x_true, int flags) {
@@ -1083,6 +1208,11 @@ int FusedEngine::run_pipelined(int max_cycles, bool& done) {
 int FusedEngine::run(int max_cycles, bool& done) {
     if (measured)
         throw StatusError(MPG_ERR_UNSUPPORTED, kMeasuredText);
+    if (!armed_)
+        throw StatusError(MPG_ERR_ARG,
+                          "the engine's matrix values were refreshed and no solve is armed on them: ||M^-1 b|| and the "
+                          "first residual depend on the new matrix, so mpg_engine_rearm must come before "
+                          "mpg_engine_run (b == NULL keeps the right-hand side)");
     try {
         return run_cycles(max_cycles, done);
     } catch (const BreakdownError& e) {
@@ -1359,6 +1489,23 @@ int mpg_engine_rearm(mpg_engine_t e, const double* b, const double* x0, const do
         return (int)MPG_OK;
     });
 }
+
+int mpg_engine_refresh_values(mpg_engine_t e, const double* val, int64_t nnz, int flags) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    const int st = mpg::engine_call(e, [&] {
+        e->eng->refresh_values(val, nnz, flags);
+        return (int)MPG_OK;
+    });
+    if (st && !e->dead && e->eng->values_dirty()) {
+        e->dead = st;
+        e->dead_error = "the engine is dead: a values refresh failed after it began overwriting the matrix (" +
+                        e->last_error + "); destroy it";
+        e->last_error = e->dead_error;
+    }
+    return st;
+}
+
+double mpg_engine_refresh_seconds(mpg_engine_t e) { return e && e->eng ? e->eng->refresh_seconds : -1.0; }
 
 int mpg_engine_x(mpg_engine_t e, double* dst, int dst_on_device) {
     if (!e || !e->eng || !dst) return MPG_ERR_ARG;

@@ -163,6 +163,18 @@ public:
     // they are. Refused (MPG_ERR_UNSUPPORTED) on a row-partitioned engine and
     // after measurement launches.
     void rearm(const double* b, const double* x0, const double* x_true, int flags);
+    // New values of A on the unchanged sparsity pattern (mpg_engine_refresh_values,
+    // solve.h): nnz fp64 values in CSR order, in host memory or on the
+    // engine's device (MPG_REFRESH_VAL_DEVICE), through the code the
+    // constructor loads its own values with. The CSR analysis, the storage
+    // layouts, the workspace, the policy and every address stay; the engine is
+    // left unarmed (rearm must follow). Refused with nothing touched: a wrong
+    // nnz (MPG_ERR_ARG), a row-partitioned or measured engine, mixed-half
+    // values the engine's kernels cannot take. A failure after that
+    // (values_dirty()) leaves the engine without a consistent matrix.
+    void refresh_values(const double* val, int64_t nnz, int flags);
+    bool values_dirty() const { return values_dirty_; }
+    double refresh_seconds = 0;  // the last refresh_values, wall clock (0: none yet)
     // rows [0, n) of x widened to fp64 into dst (host, or the engine's device); synchronises
     void copy_x(double* dst, bool dst_on_device);
     int solves() const { return solves_; }                  // arms so far, the constructor's included
@@ -210,6 +222,10 @@ private:
     std::unique_ptr<Impl> p_;
     std::unique_ptr<Convergence<double, void>> conv_;
     int solves_ = 0, graph_captures_ = 0;
+    bool armed_ = false;         // a solve is armed on the engine's current matrix (arm; refresh_values clears it)
+    bool values_dirty_ = false;  // load_values began overwriting a live engine's matrix and has not finished
+    // what depends on the values of A: the constructor's and refresh_values' one code path
+    void load_values(const double* val, bool on_device);
     // what depends on b and x: the constructor's and rearm's one code path
     void arm(const double* b, const double* x0, const double* x_true, int flags);
     void start();  // the first residual prologue of a solve and its report
@@ -247,6 +263,10 @@ struct mpg_engine {
     std::unique_ptr<mpg::Comm> comm;          // declared first: destroyed after eng
     std::unique_ptr<mpg::FusedEngine> eng;
     std::string last_error;  // the text of the last failed mpg_engine_run
+    // a values refresh that failed after it began overwriting the matrix: the
+    // engine is dead, and every call that works on the solve returns this
+    int dead = 0;
+    std::string dead_error;
 };
 
 namespace mpg {
@@ -254,6 +274,10 @@ namespace mpg {
 // the status of what it threw, with the text kept for mpg_engine_last_error.
 template <class F>
 int engine_call(mpg_engine_t e, F&& f) {
+    if (e->dead) {
+        e->last_error = e->dead_error;
+        return e->dead;
+    }
     e->last_error.clear();
     try {
         ScopedContext scope(e->ctx);

@@ -33,7 +33,10 @@
 // mpg_engine_create, then mpg_engine_rearm per further system; the stdout
 // block is printed once per solve; solve j takes x_true from --rand + j, or
 // the --bpath vector every time; without the flag, or with N = 1, the one
-// solve through mpg_solve as before).
+// solve through mpg_solve as before), --vary-values EPS (with --solves N > 1:
+// system j >= 1 has the matrix mpg_perturb_values(A, EPS, seed = j) on A's
+// pattern and b_j = A_j x_true, given to the engine by
+// mpg_engine_refresh_values before the re-arm; the stdout block is unchanged).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -74,6 +77,8 @@ int main(int argc, char* argv[]) {
     unsigned rand_seed = 42;
     int ngpus = 0;  // 0: mpg_solve on one device
     int solves = 1;
+    bool vary = false;  // --vary-values
+    double vary_eps = 0.0;
 
     for (int i = 1; i < argc; ++i) {
         const std::string f = argv[i];
@@ -103,6 +108,10 @@ int main(int argc, char* argv[]) {
         else if (f == "--device") a.device = std::stoi(next());
         else if (f == "--ngpus") ngpus = std::stoi(next());
         else if (f == "--solves") solves = std::stoi(next());
+        else if (f == "--vary-values") {
+            vary = true;
+            vary_eps = std::stod(next());
+        }
         else if (f == "--half-unscaled") a.half_unscaled = 1;
         else if (f == "--stop-on-breakdown") a.stop_on_breakdown = 1;
         else if (f == "--accum") {  // fp32 Arnoldi's accumulation class (solve.h)
@@ -167,6 +176,14 @@ int main(int argc, char* argv[]) {
         std::cout << "--solves takes a positive number of systems" << std::endl;
         return 1;
     }
+    if (vary && solves < 2) {
+        std::cout << "--vary-values changes the matrix between the systems of --solves N, N > 1" << std::endl;
+        return 1;
+    }
+    if (vary && b_path) {
+        std::cout << "--vary-values forms b_j = A_j x_true itself and cannot take --bpath" << std::endl;
+        return 1;
+    }
     if (solves > 1 && (a.engine != MPG_ENGINE_FUSED || ngpus >= 1)) {
         // (the library's rule: mpg_engine_rearm exists on the fused engine, on one GPU)
         std::cerr << "mpg_solve failed: mpgmres: a sequence of solves on one engine (--solves) runs on the fused "
@@ -225,8 +242,11 @@ int main(int argc, char* argv[]) {
         const char* banner = a.mode == MPG_MODE_MIXED || a.mode == MPG_MODE_MIXED_HALF ? "Doing Mixed Precision test"
                                                                                          : "Doing Baseline test";
         mpg_engine_t eng = nullptr;
+        const std::vector<double> val0(A.val, A.val + (vary ? A.nnz : 0));
         for (int j = 0; j < solves && st == 0; ++j) {
             if (j > 0) {
+                // --vary-values: system j's matrix, the first one's values perturbed with seed j
+                if (vary) mpg_perturb_values(val0.data(), A.nnz, vary_eps, (uint64_t)j, A.val);
                 if (!b_path) {
                     mpg_rand_vect(n, rand_seed + (unsigned)j, x_true.data());
                     mpg_host_spmv(&A, x_true.data(), b.data());
@@ -237,7 +257,8 @@ int main(int argc, char* argv[]) {
             if (j == 0) {
                 st = mpg_engine_create(&a, &eng, r.message, (int)sizeof r.message);
             } else {
-                st = mpg_engine_rearm(eng, b.data(), nullptr, x_true.data(), 0);
+                if (vary) st = mpg_engine_refresh_values(eng, A.val, A.nnz, 0);
+                if (st == 0) st = mpg_engine_rearm(eng, b.data(), nullptr, x_true.data(), 0);
                 if (st != 0) std::snprintf(r.message, sizeof r.message, "%s", mpg_engine_last_error(eng));
             }
             if (st != 0) break;

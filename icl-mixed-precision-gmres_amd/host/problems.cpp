@@ -573,6 +573,19 @@ int mpg_rand_vect(int64_t n, uint32_t seed, double* out) {
     return 0;
 }
 
+int mpg_perturb_values(const double* val, int64_t nnz, double eps, uint64_t seed, double* out) {
+    if (nnz < 0 || (nnz > 0 && (!val || !out))) return -2;
+    for (int64_t i = 0; i < nnz; ++i) {
+        const uint64_t key = mix64(seed ^ mix64((uint64_t)i));
+        const double u = (double)(key >> 11) * (2.0 / 9007199254740992.0) - 1.0;  // [-1, 1), exact
+        // (one rounding per statement: no contraction into a fused multiply-add)
+        const double t = eps * u;
+        const double f = 1.0 + t;
+        out[i] = val[i] * f;
+    }
+    return 0;
+}
+
 int mpg_host_spmv(const mpg_host_csr* a, const double* x, double* y) {
     if (!a || !x || !y) return -2;
     for (int32_t i = 0; i < a->nrows; ++i) {

@@ -86,6 +86,16 @@ typedef struct {
  * H, Givens state, two w buffers (n_ext), partials and the report block. */
 int mpg_arnoldi_create(mpg_ctx_t ctx, const mpg_arnoldi_desc* desc, mpg_arnoldi_t* out);
 int mpg_arnoldi_destroy(mpg_arnoldi_t a);
+/* The caller rewrote desc.val_inner / desc.val_outer in place (the same
+ * addresses, the same sparsity pattern, and for fp16 values the same choice of
+ * scaled or unscaled rows): every storage copy the workspace owns -- the SELL
+ * copies of the Arnoldi and the residual matrix, the node-block copies --
+ * takes the new values (mpg_sell_refresh_values and its node-block
+ * counterpart). No layout decision is taken again and no address moves, so a
+ * captured graph of the workspace's launches stays valid. CSR row-block
+ * storage reads the arrays directly: nothing to do. Launches on the context's
+ * stream, no synchronisation. */
+int mpg_arnoldi_refresh_values(mpg_arnoldi_t a);
 /* desc.block_dinv: 1 when the launches of `which` (0: the Arnoldi SpMV of every step, 1: the
  * residual prologue) apply the block inverses themselves -- node-block storage, 3 x 3 blocks -- with
  * the bits of mpg_bjacobi_apply_* on their output; 0 when the caller has to apply them */

@@ -323,6 +323,15 @@ int mpg_csr_spmv_f16f32_scaled(mpg_ctx_t ctx, mpg_csr_t A, float alpha, const ui
 int mpg_sell_create(mpg_ctx_t ctx, mpg_csr_t A, int32_t vtype, const void* vals, int32_t format,
                     mpg_sell_t* out);
 int mpg_sell_destroy(mpg_sell_t A);
+/* New values on the copy's unchanged sparsity pattern: vals (device, CSR
+ * order, every stored entry of A, the copy's own vtype -- anything else is
+ * MPG_ERR_ARG) go to the places mpg_sell_create filled, zeros into the pads,
+ * and the CSR-summed slices' rows are copied again. A is the analysed CSR
+ * the copy was created from (or one with the same row starts). Values only:
+ * the layout, the columns and every address stay, so the copy afterwards has
+ * the bits of one created from vals. Launches on the context's stream and
+ * returns without synchronising. */
+int mpg_sell_refresh_values(mpg_ctx_t ctx, mpg_sell_t S, mpg_csr_t A, int32_t vtype, const void* vals);
 int mpg_sell_layout(mpg_sell_t A, int32_t* vec_width, int32_t* col_bytes, int64_t* stored, int32_t* window);
 /* column form of the copy: 0 int32, 1 int16 slice-relative, 2 stepped int16
  * (per-(slice, step, element) bases; sell_tile.hpp); *csr_slices = slices

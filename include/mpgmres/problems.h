@@ -86,6 +86,15 @@ int mpg_load_mtx_vector(const char* path, int32_t col, double* out, int64_t n, c
  * std::uniform_real_distribution<float>, one draw per entry, widened to double. */
 int mpg_rand_vect(int64_t n, uint32_t seed, double* out);
 
+/* A sequence of matrices on one sparsity pattern (mpg_engine_refresh_values,
+ * solve.h; the CLI's --vary-values): out[i] = val[i] * (1 + eps * u_i), u_i
+ * in [-1, 1) from the generators' counter-based hash of (seed, i) --
+ * u_i = (mix64(seed ^ mix64(i)) >> 11) * 2^-52 - 1 with the splitmix64
+ * finaliser mix64 -- each product and sum rounded once. Deterministic, any
+ * slice can be formed on its own; out may be val. Returns 0, or -2 for a
+ * NULL array with nnz > 0 or nnz < 0. */
+int mpg_perturb_values(const double* val, int64_t nnz, double eps, uint64_t seed, double* out);
+
 /* y = A x, fp64, sequential row sums (host). */
 int mpg_host_spmv(const mpg_host_csr* a, const double* x, double* y);
 

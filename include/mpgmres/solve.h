@@ -176,6 +176,31 @@ const char* mpg_engine_last_error(mpg_engine_t e);
 #define MPG_ARM_B_DEVICE 1
 #define MPG_ARM_X0_DEVICE 2
 int mpg_engine_rearm(mpg_engine_t e, const double* b, const double* x0, const double* x_true, int flags);
+/* ---- new matrix values on the unchanged sparsity pattern (Newton steps, time steps, parameter sweeps) ----
+ * mpg_engine_refresh_values gives a live engine a new A with the pattern it was created with: val holds nnz fp64
+ * values in CSR order, in host memory or, with MPG_REFRESH_VAL_DEVICE in `flags`, in the memory of the engine's
+ * device (the caller's own work on them must have completed; they are only read). It runs the part of
+ * mpg_engine_create that reads the values -- the fp64 copy, the residual and the Arnoldi matrix in their types,
+ * Jacobi's diagonal, the Chebyshev interval, the GMRES-polynomial roots, the block-Jacobi inverses, the ILU factors
+ * (the factor object is made again), ||A||_F -- and refills the storage copies in place (mpg_arnoldi_refresh_values).
+ * Kept: the CSR analysis, the SELL-64 / node-block layouts, the Arnoldi workspace, the cycle policy, every address,
+ * and the captured cycle graph where none of its launch arguments changed (identity, jacobi, bjacobi, neumann); with
+ * chebyshev, gmres_poly, ilu and ilu_jacobi the graph is released and captured again by the next solve
+ * (mpg_engine_graph_captures counts it). The engine is then UNARMED: ||M^-1 b|| and the first residual depend on the
+ * new A, so mpg_engine_rearm must follow (b == NULL keeps b), and mpg_engine_run before it fails with MPG_ERR_ARG and
+ * a message that says so. The solve that follows has the bits of a new engine created on these values;
+ * mpg_engine_report's res_norm uses them. setup_seconds stays the re-arm's; mpg_engine_refresh_seconds is the
+ * duration of the last refresh (0 before the first, -1 for NULL).
+ * Nothing is touched and the engine stays usable on its old matrix when the call returns MPG_ERR_ARG (e is NULL, or
+ * nnz is not the engine's), MPG_ERR_UNSUPPORTED with the reason in mpg_engine_last_error (a row-partitioned engine;
+ * an engine that ran measurement launches; mode mixed-half where the engine was created on values that needed no row
+ * scaling -- it runs the unscaled kernels -- and the new ones need it) or MPG_ERR_RANGE (mixed-half values that do not
+ * fit fp16). The operator surface has no live engine, so no refresh. Any other failure -- an ILU zero pivot, an
+ * allocation -- comes after the overwriting began: the engine is dead, and every later call that works on the solve
+ * (run, rearm, refresh, x, report) returns that status and text; only mpg_engine_destroy is left. */
+#define MPG_REFRESH_VAL_DEVICE 1
+int mpg_engine_refresh_values(mpg_engine_t e, const double* val, int64_t nnz, int flags);
+double mpg_engine_refresh_seconds(mpg_engine_t e);
 /* rows [0, n) of the engine's iterate x widened to fp64 into dst (n entries; host memory, or the engine's device
  * where dst_on_device != 0); synchronises the engine's stream before it returns. MPG_ERR_ARG: e or dst is NULL. */
 int mpg_engine_x(mpg_engine_t e, double* dst, int dst_on_device);
