@@ -311,6 +311,7 @@ int mpg_arnoldi_prologue(mpg_arnoldi_t a) {
         return (int)MPG_OK;
     });
     a->last_part = a->partial;
+    a->last_prologue = true;
     if (st) return st;
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;

@@ -39,7 +39,12 @@ int reduce_run(mpg_arnoldi_t a, int ncols) {
     if (!a || ncols < 1 || ncols > a->d.m + 4) return MPG_ERR_ARG;
     // one column per workgroup: 256 threads when the producer left <= 512
     // partials per column (one or two loads per thread), else 1024
-    if (a->last_G <= 2 * kBlock) k_reduce_partials<kBlock, A><<<ncols, kBlock, 0, a->ctx->stream>>>(a->last_G, a->last_part, a->sums);
+    // (the once-per-cycle prologue keeps fp64 sums in the fp32 class too, arnoldi.h: the bits of
+    // mpg_arnoldi_prologue_finish_partials' own column sums)
+    if (a->last_prologue) {
+        if (a->last_G <= 2 * kBlock) k_reduce_partials<kBlock, double><<<ncols, kBlock, 0, a->ctx->stream>>>(a->last_G, a->last_part, a->sums);
+        else k_reduce_partials<1024, double><<<ncols, 1024, 0, a->ctx->stream>>>(a->last_G, a->last_part, a->sums);
+    } else if (a->last_G <= 2 * kBlock) k_reduce_partials<kBlock, A><<<ncols, kBlock, 0, a->ctx->stream>>>(a->last_G, a->last_part, a->sums);
     else k_reduce_partials<1024, A><<<ncols, 1024, 0, a->ctx->stream>>>(a->last_G, a->last_part, a->sums);
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
@@ -249,6 +254,7 @@ int spmv_run(mpg_arnoldi_t a, int k, int fold, bool dots) {
     if (dots) {
         a->last_G = a->fd_ng;
         a->last_part = a->dpart;
+        a->last_prologue = false;
     }
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
@@ -315,6 +321,7 @@ int step_dots_run(mpg_arnoldi_t a, int k, int fold) {
         if (st) return st;
         a->last_G = a->Gd;
         a->last_part = a->dpart;
+        a->last_prologue = false;
         MPG_LAUNCH_CHECK(a->ctx);
         return MPG_OK;
     } else {
@@ -399,6 +406,7 @@ int dots_run(mpg_arnoldi_t a, int k, bool combine) {
     const bool wide = !combine && ndots_all > kNC && ndots_all <= kWideMax;
     a->last_G = combine || ndots_all <= kNC ? a->Gd : wide ? wide_groups(a, ndots_all) : row_grid(a);
     a->last_part = !combine && ndots_all <= kWideMax ? a->dpart : a->partial;
+    a->last_prologue = false;
     if (st) return st;
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
@@ -598,6 +606,7 @@ int cgs_run(mpg_arnoldi_t a, int k, int pass, bool givens, bool from_partials, b
     });
     a->last_G = next_dots || givens ? row_grid(a) : a->Gd;
     a->last_part = a->partial;
+    a->last_prologue = false;
     if (st) return st;
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;
@@ -623,6 +632,7 @@ int mgs_run(mpg_arnoldi_t a, int k, int j, bool from_partials) {
     });
     a->last_G = a->Gd;
     a->last_part = dst;
+    a->last_prologue = false;
     if (st) return st;
     MPG_LAUNCH_CHECK(a->ctx);
     return MPG_OK;

@@ -333,6 +333,16 @@ __global__ __launch_bounds__(BS) void k_cgs_update(int n, const T* __restrict__ 
                                                        T* __restrict__ w, double* __restrict__ partial,
                                                        unsigned* __restrict__ cnt, GivensArgs<T> g, int part_G) {
     static_assert(!(NEXT_DOTS && GIVENS), "the Givens step follows the last pass");
+    // GIVENS: the last-arriving workgroup's givens_block reads the column workgroup 0 stores here, and the
+    // XCDs' L2s are not coherent: a plain store may stay in workgroup 0's L2, where another XCD's acquire does
+    // not reach it. Seen once (tests/test_arnoldi_phases_gpu.py::test_cgs_from_sums, cgs_givens at k + 1 = 9):
+    // the step had rotated the column's old contents and stored that over the coefficients; the cause is read
+    // from the code, not demonstrated. Write-through, as the partials (handoff.hpp; drained ahead of the
+    // ticket by last_arriver's vmcnt(0))
+    auto store_coef = [](T* p, T c) {
+        if constexpr (GIVENS) store_wt(p, c);
+        else *p = c;
+    };
     __shared__ A coef[256];
     const int nc = k + 1;
     const int n4 = n & ~3;
@@ -370,13 +380,13 @@ __global__ __launch_bounds__(BS) void k_cgs_update(int n, const T* __restrict__ 
         if (j < nc && sub == 0) {
             const T c = (T)v;
             coef[j] = (A)c;
-            if (blockIdx.x == 0) coef_out[j] = c;
+            if (blockIdx.x == 0) store_coef(coef_out + j, c);
         }
     } else {
         for (int j = threadIdx.x; j < nc; j += BS) {
             const T c = (T)sums[j];
             coef[j] = (A)c;
-            if (blockIdx.x == 0) coef_out[j] = c;
+            if (blockIdx.x == 0) store_coef(coef_out + j, c);
         }
     }
     __syncthreads();

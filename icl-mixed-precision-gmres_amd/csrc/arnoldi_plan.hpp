@@ -100,6 +100,9 @@ struct mpg_arnoldi {
     int Grb = 1;      // workgroups of the row-block (SpMV) kernels: one per row block
     int last_G = 1;   // partial count per column written by the last producer
     double* last_part = nullptr;  // ... and the buffer it wrote (partial or dpart)
+    // ... which hold the residual prologue's fp64 sums (set by mpg_arnoldi_prologue, cleared by every
+    // other producer): mpg_arnoldi_reduce adds them in fp64 in either accumulation class
+    bool last_prologue = false;
     int64_t ld = 0;   // leading dimension of V (elements)
     size_t tsize = 8;
     void* V = nullptr;

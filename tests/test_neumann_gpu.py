@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from tests import parity
+from tests.arnoldi_phase import PhaseWorkspace
 from tests.test_neumann_cpu import np_solve, np_sweep
 from tests.test_step_dots_waves_gpu import _edge_matrix
 
@@ -180,40 +181,15 @@ def test_sell_sweep_bits(mpg, hip, case, t):
 MPG_F64, MPG_F32 = 0, 1
 
 
-class Workspace:
+class Workspace(PhaseWorkspace):
     """mpg_arnoldi_create on A with no preconditioner inside the launches and
-    Jacobi's inverse diagonal in the descriptor (what prec="neumann" sets up)."""
+    Jacobi's inverse diagonal in the descriptor (what prec="neumann" sets up):
+    tests/arnoldi_phase.py's workspace at its defaults, on this file's Storage.
+    (Inherited with it: a HIP runtime error in a copy or launch made through
+    the helper's own methods ends the pytest session, PhaseWorkspace._check.)"""
 
     def __init__(self, mpg, hip, A, t, fmt, accum):
-        from mpgmres_amd._abi import ArnoldiDesc
-
-        self.hip, self.n, self.t = hip, A.nrows, t
-        self.T, self.ct, vt = TYPES[t]
-        self.S = Storage(hip, A, t, sell=fmt == 2)
-        n = self.n
-        self.val64 = hip.buf(A.val)
-        self.diag = hip.buf(n, self.T)
-        hip.call(f"mpg_jacobi_setup_{t}", self.S.csr, self.S.vals.p, self.diag.p)
-        self.b, self.x = hip.buf(np.ones(n)), hip.buf(np.zeros(n))
-        d = ArnoldiDesc()
-        d.n, d.n_ext, d.m, d.orth = n, n, 4, 0
-        d.vec_type = d.prec_type = d.inner_val = vt
-        d.outer_type = MPG_F64
-        d.jacobi = 0
-        d.A = self.S.csr.value
-        d.val_outer = (self.val64 if t == "f32" else self.S.vals).p.value
-        d.val_inner = self.S.vals.p.value
-        d.diag = self.diag.p.value
-        d.b, d.x = self.b.p.value, self.x.p.value
-        d.spmv_format = fmt
-        self.arn = C.c_void_p()
-        hip.call("mpg_arnoldi_create", C.byref(d), C.byref(self.arn))
-        hip.check(hip.lib.mpg_arnoldi_set_accum(self.arn, accum), "set_accum")
-        f = C.c_int32()
-        hip.check(hip.lib.mpg_arnoldi_spmv_layout(self.arn, C.byref(f), None, None, None, None), "layout")
-        self.format = f.value
-        one = np.ones(1, self.T)  # 1/h: the Arnoldi SpMV then forms A w_prev itself
-        hip.check(hip.lib.mpg_memcpy_h2d(hip.ctx, hip.lib.mpg_arnoldi_inv_dev(self.arn), one.ctypes.data, one.nbytes))
+        super().__init__(mpg, hip, A, t, fmt, accum, storage=Storage(hip, A, t, sell=fmt == 2))
 
     def spmv(self, x):
         """T(A x) in the workspace's accumulation class: its own Arnoldi SpMV."""
@@ -235,10 +211,8 @@ class Workspace:
         return got
 
     def close(self):
-        self.hip.lib.mpg_arnoldi_destroy(self.arn)
+        super().close()
         self.S.close()
-        for b in (self.val64, self.diag, self.b, self.x):
-            b.free()
 
 
 APPLY_CASES = [("band_4352", 2), ("stencil27_5", 1), ("stencil27_5", 3)]  # (matrix, mpg_arnoldi_desc.spmv_format)
