@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-MPG_F64, MPG_F32 = 0, 1
+MPG_F64, MPG_F32, MPG_F16 = 0, 1, 2
 TYPES = {"f64": (np.float64, C.c_double, MPG_F64), "f32": (np.float32, C.c_float, MPG_F32)}  # dtype, ctype, mpg_dtype_t
 ORTH = {"cgs": 0, "mgs": 1, "cgsr": 2}
 MPG_OK, MPG_ERR_HIP, MPG_ERR_UNSUPPORTED = 0, -1, -5
@@ -32,6 +32,125 @@ MATRICES = {
 }
 
 
+# ---------------------------------------------------------------- the variants' matrices (seeded, hand-built)
+FAR = 32_900            # far33k's far columns: r +- FAR, beyond the int16 slice-relative form's +-32767
+FAR66_ROW, FAR66 = 33_024, 33_000  # far66k: element 0 of row FAR66_ROW is r - FAR66, of the next row r + FAR66
+RANK_SPLITS = {"band-ranks": [0, 4099, 8198, 12297], "band-stiff-ranks": [0, 4099, 8198, 12297],
+               "stencil-ranks": [0, 324, 648]}
+
+
+def _csr_of(mpg, n, rows, cols, vals):
+    import scipy.sparse as sp
+
+    M = sp.csr_matrix((vals, (rows, cols)), shape=(n, n))
+    M.sort_indices()
+    return mpg.Csr(n, n, M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data.astype(np.float64))
+
+
+def _tridiag(n, seed):
+    """(rows, cols, vals) of a tridiagonal matrix: diagonal uniform in [3, 5], off-diagonals in [-1, -0.5]."""
+    rng = np.random.default_rng(seed)
+    r = np.arange(n)
+    rows = np.concatenate([r, r[1:], r[:-1]])
+    cols = np.concatenate([r, r[1:] - 1, r[:-1] + 1])
+    vals = np.concatenate([rng.uniform(3.0, 5.0, n), rng.uniform(-1.0, -0.5, 2 * (n - 1))])
+    return rows, cols, vals, rng
+
+
+def gen_far33k(mpg, n=33_280):
+    """Tridiagonal plus entries at column r +- FAR wherever that is in range:
+    col - (first row of the slice) leaves +-32767 (the stepped int16 form), and
+    no (step, element) position of a slice spreads beyond 65,534 (no slice is
+    summed from the sub-CSR)."""
+    rows, cols, vals, rng = _tridiag(n, 33)
+    r = np.arange(n)
+    lo, hi = r[r - FAR >= 0], r[r + FAR < n]
+    rows = np.concatenate([rows, lo, hi])
+    cols = np.concatenate([cols, lo - FAR, hi + FAR])
+    vals = np.concatenate([vals, rng.uniform(0.25, 0.75, len(lo) + len(hi))])
+    return _csr_of(mpg, n, rows, cols, vals)
+
+
+def gen_far66k(mpg, n=66_048):
+    """Tridiagonal; row FAR66_ROW also reads column r - FAR66 (its element 0),
+    and the next row holds only column r + FAR66 (its element 0): that slice's
+    element 0 spreads over 66,000 and the slice is summed from the sub-CSR
+    (tests/test_sell_stepped_gpu.py::_far, shrunk)."""
+    rows, cols, vals, rng = _tridiag(n, 66)
+    keep = rows != FAR66_ROW + 1
+    rows, cols, vals = rows[keep], cols[keep], vals[keep]
+    rows = np.concatenate([rows, [FAR66_ROW, FAR66_ROW + 1]])
+    cols = np.concatenate([cols, [FAR66_ROW - FAR66, FAR66_ROW + 1 + FAR66]])
+    vals = np.concatenate([vals, [0.25, 0.5]])
+    return _csr_of(mpg, n, rows, cols, vals)
+
+
+def gen_band_stiff(mpg, n=4099):
+    """gen_band(n) with every 7th row times 2^20 and every 11th row times 2^-12:
+    rows that mpg_csr_half_values scales down, scales up and leaves alone share
+    64-row slices."""
+    A = mpg.gen_band(n, 5, 4, seed=7)
+    r = np.arange(A.nrows)
+    f = np.where(r % 7 == 0, 2.0 ** 20, 1.0) * np.where(r % 11 == 0, 2.0 ** -12, 1.0)
+    return mpg.Csr(A.nrows, A.ncols, A.rowptr, A.col, A.val * np.repeat(f, np.diff(A.rowptr)))
+
+
+def gen_stencil_rows(mpg, nx=5):
+    """gen_stencil27(nx) with row i scaled by a factor in [0.5, 2] of its own: the 3 x 3 diagonal blocks, which
+    the stencil has symmetric, lose their symmetry, and so do their inverses (block Jacobi read transposed)."""
+    A = mpg.gen_stencil27(nx)
+    f = np.random.default_rng(27).uniform(0.5, 2.0, A.nrows)
+    return mpg.Csr(A.nrows, A.ncols, A.rowptr, A.col, A.val * np.repeat(f, np.diff(A.rowptr)))
+
+
+MATRICES.update({
+    "stencil5-rows": gen_stencil_rows,
+    "far33k": gen_far33k, "far66k": gen_far66k, "band-stiff": gen_band_stiff,
+    "band-stiff8197": lambda m: gen_band_stiff(m, 8197),          # every slice as wide: two slices per wave
+    "band-stiff-ranks": lambda m: gen_band_stiff(m, 3 * 4099),    # (RANK_SPLITS)
+    "band-ranks": lambda m: m.gen_band(3 * 4099, 5, 4, seed=7),  # split into three row blocks (RANK_SPLITS)
+    "stencil-ranks": lambda m: m.gen_stencil27(6),               # two row blocks of 108 nodes: a gathered halo
+})
+
+
+class RankBlock:
+    """Rows row_starts[rank] .. row_starts[rank + 1] of A as the row-partitioned
+    engine holds them: local column ids from HaloPlan.local_cols() (lower
+    ranks' halo rows at [-n_front, 0), higher ranks' at [n, n_ext)).
+    .A: the local matrix (ncols = n_ext); .glob: the global row of each local id
+    in [-n_front, n_ext) (index local + n_front); .own: this rank's global rows."""
+
+    def __init__(self, mpg, A, row_starts, rank):
+        r0, r1 = int(row_starts[rank]), int(row_starts[rank + 1])
+        p0, p1 = int(A.rowptr[r0]), int(A.rowptr[r1])
+        gcol = np.ascontiguousarray(A.col[p0:p1], np.int32)
+        rp = np.ascontiguousarray(A.rowptr[r0:r1 + 1] - p0, np.int32)
+        val = np.ascontiguousarray(A.val[p0:p1], np.float64)
+        plan = mpg.HaloPlan(rank, len(row_starts) - 1, np.asarray(row_starts, np.int64),
+                            mpg.Csr(r1 - r0, A.ncols, rp, gcol, val))
+        self.n, self.n_ext, self.n_front = r1 - r0, plan.n_ext, plan.n_front
+        lcol = plan.local_cols()
+        plan.close()
+        self.A = mpg.Csr(self.n, self.n_ext, rp, lcol, val)
+        self.glob = np.full(self.n_front + self.n_ext, -1, np.int64)
+        self.glob[lcol.astype(np.int64) + self.n_front] = gcol
+        self.glob[self.n_front:self.n_front + self.n] = np.arange(r0, r1)
+        assert np.all(self.glob >= 0), "a halo id no column uses"
+        self.own = np.arange(r0, r1)
+
+    def to_scipy(self):
+        """n x (n_front + n_ext), the columns shifted by n_front."""
+        import scipy.sparse as sp
+
+        return sp.csr_matrix((self.A.val, self.A.col.astype(np.int64) + self.n_front, self.A.rowptr),
+                             shape=(self.n, self.n_front + self.n_ext))
+
+
+def front_pad(n_front):
+    """MPG_FRONT_PAD of arnoldi.h: entries allocated in front of row 0 of a vector with a lower halo."""
+    return (n_front + 63) // 64 * 64 + 64 if n_front > 0 else 0
+
+
 def ld_of(n, itemsize):
     """mpg_arnoldi_create's leading dimension: columns padded to 256 B
     (asserted against the workspace's own in PhaseWorkspace)."""
@@ -47,6 +166,7 @@ _DECLS = {  # what the package's own table leaves undeclared
     "step_dots_supported": [_P, _I], "cgs_stream_at": [_P, _I], "prologue_finish": [_P], "slices_per_wave": [_P],
     "num_groups": [_P], "accum": [_P], "partials_count": [_P], "prologue_format": [_P],
     "sell_columns": [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "prec_fused": [_P, _I], "uniform_groups": [_P],
 }
 
 
@@ -81,10 +201,22 @@ class PhaseWorkspace:
 
     storage: an object with .csr and .vals (A's values in T) to build on;
     else the workspace makes and owns one. MPG_CGS_PREFETCH and MPG_SELL_PAIR
-    are read at create: set them (monkeypatch) first."""
+    are read at create: set them (monkeypatch) first.
+
+    Halo rows (n_ext > n, n_front > 0): A holds one rank's rows with local
+    column ids in [-n_front, n_ext) and A.ncols = n_ext, as the row-partitioned
+    engine passes them (host/fused_gmres.cpp); x has front_pad(n_front) + n_ext
+    entries and the descriptor points at its row 0. The ext=True forms of
+    put_w / get_w / put_x / get_x cover [-n_front, n_ext); the put forms also
+    fill the pad in front of -n_front (`pad`).
+    inner_val=MPG_F16: the Arnoldi values are mpg_csr_half_values' copy of A's
+    fp64 values, scaled per row (row_exp=1) or not (0); the exponents go into
+    the descriptor only when a row was scaled, as the engine does.
+    prec_block: mpg_bjacobi_setup_*'s inverses of the diagonal blocks go into
+    the descriptor as block_dinv (jacobi must be 0)."""
 
     def __init__(self, mpg, hip, A, t="f32", spmv_format=1, accum=0, *, m=4, orth=0, jacobi=0, basis=0, x=None,
-                 b=None, storage=None):
+                 b=None, storage=None, n_ext=None, n_front=0, inner_val=None, row_exp=1, prec_block=0):
         from mpgmres_amd._abi import ArnoldiDesc
 
         _declare(hip.lib)
@@ -97,9 +229,15 @@ class PhaseWorkspace:
         self.diag = hip.buf(n, self.T)
         hip.call(f"mpg_jacobi_setup_{t}", self.S.csr, self.S.vals.p, self.diag.p)
         self.b = hip.buf(np.ones(n) if b is None else np.asarray(b, np.float64))
-        self.x = hip.buf(np.zeros(n) if x is None else np.asarray(x, np.float64))
+        self.n_ext, self.n_front = n if n_ext is None else n_ext, n_front
+        self.front = front_pad(n_front)
+        assert self.n_ext >= n and n_front >= 0 and A.ncols == self.n_ext, (n, self.n_ext, n_front, A.ncols)
+        self.x = hip.buf(np.zeros(self.front + self.n_ext))
+        self.xp = self.x.p.value + 8 * self.front  # row 0
+        if x is not None:
+            self.put_x(x, ext=len(x) != n)
         d = ArnoldiDesc()
-        d.n, d.n_ext, d.m, d.orth = n, n, m, ORTH.get(orth, orth)
+        d.n, d.n_ext, d.n_front, d.m, d.orth = n, self.n_ext, n_front, m, ORTH.get(orth, orth)
         d.vec_type = d.prec_type = d.inner_val = vt
         d.outer_type = MPG_F64
         d.jacobi = jacobi
@@ -107,10 +245,31 @@ class PhaseWorkspace:
         d.val_outer = (self.val64 if t == "f32" else self.S.vals).p.value
         d.val_inner = self.S.vals.p.value
         d.diag = self.diag.p.value
-        d.b, d.x = self.b.p.value, self.x.p.value
+        d.b, d.x = self.b.p.value, self.xp
         d.spmv_format = spmv_format
+        self.half = self.rexp = self.dinv = None
+        if inner_val == MPG_F16:
+            self.half, self.rexp = hip.buf(A.nnz, np.uint16), hip.buf(n + 64, np.int8)
+            stats = (C.c_int64 * 4)()
+            self._check(self.lib.mpg_csr_half_values(hip.ctx, self.S.csr, self.val64.p, row_exp, self.half.p,
+                                                     self.rexp.p if row_exp else None, stats), "mpg_csr_half_values")
+            self.half_stats = list(stats)
+            d.inner_val, d.val_inner = MPG_F16, self.half.p.value
+            if row_exp and stats[0] > 0:  # rows all in range: the unscaled kernels (host/fused_gmres.cpp)
+                d.inner_row_exp = self.rexp.p.value
+        if prec_block:
+            self.dinv = hip.buf(np.zeros(n * prec_block, self.T))
+            bad = C.c_int32(-7)
+            self._check(getattr(self.lib, f"mpg_bjacobi_setup_{t}")(hip.ctx, self.S.csr, self.S.vals.p, prec_block,
+                                                                    self.dinv.p, C.byref(bad)), "mpg_bjacobi_setup")
+            assert bad.value == -1, f"mpg_bjacobi_setup: diagonal block {bad.value} is singular"
+            d.block_dinv, d.prec_block = self.dinv.p.value, prec_block
         self.arn = C.c_void_p()
-        hip.call("mpg_arnoldi_create", C.byref(d), C.byref(self.arn))
+        try:  # (a HIP runtime error ends the session in _check; a refused descriptor raises RuntimeError)
+            self._check(self.lib.mpg_arnoldi_create(hip.ctx, C.byref(d), C.byref(self.arn)), "mpg_arnoldi_create")
+        except RuntimeError:  # nothing of a refused descriptor stays behind
+            self.close()
+            raise
         hip.check(self.lib.mpg_arnoldi_set_accum(self.arn, accum), "set_accum")
         if basis:
             hip.check(self.lib.mpg_arnoldi_set_basis(self.arn, basis), "set_basis")
@@ -159,13 +318,25 @@ class PhaseWorkspace:
     def get_V(self, j):
         return self._get(self._V, self.n, self.VT, j * self.ld)
 
-    def put_w(self, k, w):
-        """The input vector of step k (the other buffer is step k's output)."""
-        assert len(w) == self.n
-        self._put(self.lib.mpg_arnoldi_wprev_dev(self.arn, k), w, self.T)
+    def _ext(self, v, pad):
+        """[-front_pad, n_ext) from the n_front + n_ext entries of v, `pad` in front of -n_front."""
+        assert len(v) == self.n_front + self.n_ext
+        return np.concatenate([np.full(self.front - self.n_front, pad), np.asarray(v, np.float64)])
 
-    def get_w(self, k):
-        return self._get(self.lib.mpg_arnoldi_wprev_dev(self.arn, k), self.n, self.T)
+    def put_w(self, k, w, ext=False, pad=np.nan):
+        """The input vector of step k (the other buffer is step k's output).
+        ext: rows [-n_front, n_ext), and `pad` in the entries in front of them."""
+        ptr = self.lib.mpg_arnoldi_wprev_dev(self.arn, k)
+        if ext:
+            return self._put(ptr, self._ext(w, pad), self.T, -self.front)
+        assert len(w) == self.n
+        self._put(ptr, w, self.T)
+
+    def get_w(self, k, ext=False):
+        ptr = self.lib.mpg_arnoldi_wprev_dev(self.arn, k)
+        if ext:
+            return self._get(ptr, self.n_front + self.n_ext, self.T, -self.n_front)
+        return self._get(ptr, self.n, self.T)
 
     def put_H(self, H):
         assert H.shape == (self.m + 1, self.m)
@@ -205,12 +376,16 @@ class PhaseWorkspace:
         return self._get(self.lib.mpg_arnoldi_report_dev(self.arn), self.lib.mpg_arnoldi_report_len(self.arn),
                          np.float64)
 
-    def put_x(self, x):
+    def put_x(self, x, ext=False, pad=np.nan):
+        if ext:
+            return self._put(self.xp, self._ext(x, pad), np.float64, -self.front)
         assert len(x) == self.n
-        self._put(self.x.p.value, x, np.float64)
+        self._put(self.xp, x, np.float64)
 
-    def get_x(self):
-        return self.x.get()
+    def get_x(self, ext=False):
+        if ext:
+            return self._get(self.xp, self.n_front + self.n_ext, np.float64, -self.n_front)
+        return self._get(self.xp, self.n, np.float64)
 
     def put_b(self, b):
         assert len(b) == self.n
@@ -246,9 +421,36 @@ class PhaseWorkspace:
         self.hip.check(self.lib.mpg_arnoldi_sell_columns(self.arn, C.byref(form), None, None), "sell_columns")
         return form.value
 
+    def prec_fused(self, which):
+        """mpg_arnoldi_prec_fused: 1 when the launches of `which` (0 the SpMV, 1 the prologue) apply block_dinv."""
+        return self.lib.mpg_arnoldi_prec_fused(self.arn, which)
+
+    def uniform_groups(self):
+        """As the row-partitioned engine does once after create: the same partial count on every rank."""
+        self._check(self.lib.mpg_arnoldi_uniform_groups(self.arn), "mpg_arnoldi_uniform_groups")
+
+    def half_bits(self):
+        """The device's fp16 copy of the values (CSR order)."""
+        return self._get(self.half.p.value, self.half.n, np.uint16)
+
+    def row_exp(self):
+        """The device's per-row exponents of the fp16 copy."""
+        return self._get(self.rexp.p.value, self.n, np.int8)
+
+    def block_dinv(self):
+        """The device's inverses of the diagonal blocks (prec_block values per row, row-major per block)."""
+        return self._get(self.dinv.p.value, self.dinv.n, self.T)
+
+    def sell_columns(self):
+        """(form, CSR-summed slices) of mpg_arnoldi_sell_columns."""
+        form, exc = C.c_int32(), C.c_int64()
+        self._check(self.lib.mpg_arnoldi_sell_columns(self.arn, C.byref(form), C.byref(exc), None), "sell_columns")
+        return form.value, exc.value
+
     def close(self):
         self.lib.mpg_arnoldi_destroy(self.arn)
         if self.own:
             self.S.close()
-        for buf in (self.val64, self.diag, self.b, self.x):
-            buf.free()
+        for buf in (self.val64, self.diag, self.b, self.x, self.half, self.rexp, self.dinv):
+            if buf is not None:
+                buf.free()

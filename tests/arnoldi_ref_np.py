@@ -105,18 +105,89 @@ def gen_rotations(m, seed, dtype=np.float32):
 
 
 # ---------------------------------------------------------------- phases
-def ref_spmv_step(A64, w_prev, inv, diag=None):
+def ref_spmv_step(A64, w_prev, inv, diag=None, n_front=0):
     """v = T(w_prev * inv) (one multiply in T: exact bits), w = A v in fp64
-    (d o (A v) with diag), and scale = |d| o (|A| |v|)."""
+    (d o (A v) with diag), and scale = |d| o (|A| |v|).
+    With halo rows w_prev has n_front + n_ext entries (local ids [-n_front,
+    n_ext)) and A64 is n x (n_front + n_ext), its columns shifted by n_front:
+    v_ext = T(w_prev * inv) over all of them, the rows are summed in fp64 over
+    v_ext, and the v returned -- what V(:,k) must hold, bit for bit -- is
+    v_ext on the rows [0, n) only."""
     T = w_prev.dtype
-    v = (w_prev * T.type(inv)).astype(T)
-    v64 = v.astype(np.float64)
+    n = A64.shape[0]
+    assert A64.shape[1] == len(w_prev) and n_front + n <= len(w_prev)
+    v_ext = (w_prev * T.type(inv)).astype(T)
+    v64 = v_ext.astype(np.float64)
     w = np.asarray(A64 @ v64)
     scale = np.asarray(abs(A64) @ np.abs(v64))
     if diag is not None:
         d = np.asarray(diag, np.float64)
         w, scale = d * w, np.abs(d) * scale
-    return v, w, scale
+    return v_ext[n_front:n_front + n], w, scale
+
+
+def half_values(A, scale=1, n_front=0):
+    """mpg_csr_half_values' rule (capi.h) on A's fp64 values: e_i = 0 when the
+    row's largest finite |a_ij| lies in [2^-2, 2^15) (or scale == 0, or the
+    row holds no nonzero), else e_i = 14 - floor(log2 max |a_ij|); the stored
+    entry is fp16_rne(fp32_rne(a_ij 2^e_i)) (the two roundings of the device's
+    cast). Returns the fp16 bits (CSR order), e (int64 per row) and the fp64
+    SciPy matrix of float(h_ij) 2^-e_i -- what a SpMV over the copy multiplies:
+    it forms the row sum of the h_ij and unscales it by the power of two, which
+    commutes with every rounding in the normal range, so the reference row sum
+    is formed over this matrix and the bound of a T-valued matrix carries over.
+    n_front: A's columns are local ids in [-n_front, A.ncols); the matrix
+    returned is n x (n_front + A.ncols), the columns shifted by n_front."""
+    n = A.nrows
+    rows = np.repeat(np.arange(n), np.diff(A.rowptr))
+    a = np.abs(A.val)
+    fin = np.isfinite(a)
+    m = np.zeros(n)
+    np.maximum.at(m, rows[fin], a[fin])
+    e = np.zeros(n, np.int64)
+    if scale:
+        E = np.frexp(np.where(m > 0, m, 1.0))[1] - 1  # floor(log2 m): m = f 2^x, f in [0.5, 1)
+        out = (m > 0) & ((E < -2) | (E > 14))
+        e[out] = 14 - E[out]
+    with np.errstate(over="ignore"):
+        h = np.ldexp(A.val, e[rows]).astype(np.float32).astype(np.float16)
+    M = sp.csr_matrix((np.ldexp(h.astype(np.float64), -e[rows]), A.col.astype(np.int64) + n_front, A.rowptr),
+                      shape=(n, n_front + A.ncols))
+    return h.view(np.uint16), e, M
+
+
+def ref_node_bj(A64, w_prev, inv, dinv):
+    """k_step_node_bj (arnoldi_spmv.hpp): v = T(w_prev * inv); every row sum
+    t_i = (A v)_i is rounded to T and taken to P; then, per 3 x 3 block, row i
+    of w = Dinv t is formed in P as ((d_i0 t_0 + d_i1 t_1) + d_i2 t_2), each
+    product rounded, summed left to right, no contraction, and stored as T.
+    dinv: mpg_bjacobi_setup_*'s 3 values per row, row-major per block. Here t
+    and w = Dinv t are exact fp64 sums; beside them the magnitudes
+    tol_node_bj is built from: scale = |A| |v| and absDt = |Dinv| |t|."""
+    v, t, scale = ref_spmv_step(A64, w_prev, inv)
+    n = len(t)
+    assert n % 3 == 0 and len(dinv) == 3 * n
+    D = np.asarray(dinv, np.float64).reshape(n // 3, 3, 3)
+    w = np.einsum("bij,bj->bi", D, t.reshape(-1, 3)).reshape(-1)
+    absDt = np.einsum("bij,bj->bi", np.abs(D), np.abs(t).reshape(-1, 3)).reshape(-1)
+    return dict(v=v, t=t, scale=scale, w=w, absDt=absDt, absD=np.abs(D))
+
+
+def tol_node_bj(R, terms, T, P, acc32):
+    """The bound of ref_node_bj's w, from k_step_node_bj's statement. The
+    device's t^_j = P(T(sum_j)) differs from t_j by at most delta_j = u_T |t_j|
+    + (terms + 1) (u_A + 2^-53) scale_j (the plain SpMV's bound: the row sum in
+    the class A and the restatement's own fp64 sum, then the rounding to T; P
+    holds T exactly or is wider). Through the exact product that is |Dinv|
+    delta. The three products and two adds in P put at most three roundings on
+    each term: 3 u_P |Dinv| (|t| + delta) (Higham, Accuracy and Stability,
+    eq. 3.4 with gamma_3 <= 3 u (1 + 2^-20)). The store to T: u_T |w|. And the
+    restatement's own 3-term fp64 sum: 3 2^-53 |Dinv| |t|."""
+    ua = 2.0 ** -24 if acc32 else 2.0 ** -53
+    delta = unit(T) * np.abs(R["t"]) + (terms + 1) * (ua + 2.0 ** -53) * R["scale"]
+    Dd = np.einsum("bij,bj->bi", R["absD"], delta.reshape(-1, 3)).reshape(-1)
+    return ((Dd + 3 * unit(P) * (R["absDt"] + Dd) + unit(T) * np.abs(R["w"])) * (1 + 2.0 ** -20)
+            + 3 * 2.0 ** -53 * R["absDt"])
 
 
 def ref_dots(V, w):
@@ -189,19 +260,27 @@ def ref_update(V, H, s, k, x):
                 absVg=(np.abs(V64) @ g.astype(LD)).astype(np.float64))
 
 
-def ref_prologue(A64, b, x, T, diag=None):
+def ref_prologue(A64, b, x, T, diag=None, n_front=0):
     """r = b - A x in fp64 with its cancellation scale |b| + |A| |x|; w0 =
     T(r), with Jacobi T(d o T(r)); r_norm = ||T(r)||, beta = ||w0|| rounded to
-    T, x_norm; inv_beta = T(1) / beta."""
+    T, x_norm; inv_beta = T(1) / beta.
+    With halo rows x has n_front + n_ext entries and A64 is n x (n_front +
+    n_ext) (ref_spmv_step's layout): the rows are summed over all of x, and
+    x_norm is taken over the rows [0, n) only -- every k_prologue* adds x_i^2
+    in the epilogue of row i, i < n, next to that row's own T(r)_i^2 and w_i^2
+    (arnoldi_prologue.hpp), so a rank's three partials cover its own rows and
+    the all-reduce over ranks counts each global row once."""
     T = np.dtype(T).type
-    b64, x64 = np.asarray(b, np.float64), np.asarray(x, np.float64)
-    r = b64 - np.asarray(A64 @ x64)
-    scale = np.abs(b64) + np.asarray(abs(A64) @ np.abs(x64))
+    b64, x_all = np.asarray(b, np.float64), np.asarray(x, np.float64)
+    assert A64.shape[1] == len(x_all)
+    x_own = x_all[n_front:n_front + A64.shape[0]]
+    r = b64 - np.asarray(A64 @ x_all)
+    scale = np.abs(b64) + np.asarray(abs(A64) @ np.abs(x_all))
     tr = r.astype(T)
     w0 = tr if diag is None else (np.asarray(diag, T) * tr).astype(T)
     nrm = lambda v: float(np.sqrt((v.astype(LD) ** 2).sum()))
     beta = T(nrm(w0))
-    return dict(r=r, scale=scale, w0=w0, r_norm=float(T(nrm(tr))), beta=float(beta), x_norm=nrm(x64),
+    return dict(r=r, scale=scale, w0=w0, r_norm=float(T(nrm(tr))), beta=float(beta), x_norm=nrm(x_own),
                 inv_beta=float(T(1) / beta), nnz_row=int(np.diff(A64.indptr).max()))
 
 
@@ -235,6 +314,27 @@ def tol_rows(ref, t, scale, terms, T, acc32):
     second-order terms.)"""
     ua = 2.0 ** -24 if acc32 else 2.0 ** -53
     return (unit(T) * (np.abs(ref) + np.abs(t)) + (terms + 1) * ua * scale) * (1 + 2.0 ** -20) + REF * np.abs(ref)
+
+
+def tol_spmv(ref, scale, terms, T, acc32, jacobi=0):
+    """w = M(A v) against ref_spmv_step's fp64 row sums (the expression of
+    tests/test_arnoldi_phases_gpu.py::_check_spmv): tol_rows' sum term over
+    the row's entries in the class A, the restatement's own fp64 row sum
+    ((terms + 1) 2^-53 scale), and one rounding to T (three with Jacobi: the
+    row sum, d * w and its store)."""
+    ua = 2.0 ** -24 if acc32 else 2.0 ** -53
+    return ((3 if jacobi else 1) * unit(T) * np.abs(ref) + (terms + 1) * (ua + 2.0 ** -53) * scale) * (1 + 2.0 ** -20)
+
+
+def tol_prologue_w0(P, T, diag=None):
+    """w0 = M(T(b - A x)) against ref_prologue (test_prologue's expression): r
+    is an fp64 sum of nnz products and one subtraction, (nnz + 2) 2^-53 (|b| +
+    |A| |x|) whatever the order, twice (the device's evaluation and the
+    restatement's own); then T(r), and with Jacobi d * T(r) rounded to T."""
+    u = unit(T)
+    dr = 2 * (P["nnz_row"] + 2) * 2.0 ** -53 * P["scale"]
+    d = np.abs(np.asarray(diag, np.float64)) if diag is not None else 1.0
+    return d * (dr + u * np.abs(P["r"])) * (1 + 2 * u) + u * np.abs(P["w0"])
 
 
 def tol_update(R, k, x_ref, T, X, acc32):

@@ -27,11 +27,11 @@ Entry points and the cases that cover them:
   update_tail                                           test_update_tail
   reduce                                                every sum below
   compressed basis (dots, cgs_partials, update)         test_basis16
-Not covered: the stepped int16 column form of the SELL copy, which is built
-only where a slice's columns span more than 32767 (from 216,600 rows in
-tests/test_sell_stepped_gpu.py; gen_stencil27(5) gets plain int16 columns);
-n_front > 0 (halo rows), fp16 matrix values, block Jacobi inside
-the node launches: out of this file's scope (one rank, mixed and baseline)."""
+Not covered here (one rank, fp32 / fp64 values, plain int16 or int32 SELL
+columns): the stepped int16 column form of the SELL copy, halo rows (n_front
+> 0, n_ext > n), fp16 matrix values and block Jacobi inside the node launches
+are tests/test_arnoldi_variants_gpu.py's, by the same method; its header
+lists what remains uncovered after both files."""
 import functools
 
 import numpy as np

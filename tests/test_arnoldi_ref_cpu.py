@@ -32,13 +32,27 @@ without a GPU.
     one row leaves its bound; a column mutation must move at least a quarter
     of the rows by 4 bounds (not every row can: two entries of random
     magnitude may lie close, and with 130 columns in the fp32 class the row
-    bound is (terms + 1) u_32 wide)."""
+    bound is (terms + 1) u_32 wide).
+(c) The storage variants (tests/test_arnoldi_variants_gpu.py). The generators
+    give what the GPU cases rely on: front_pad is arnoldi.h's macro; far33k
+    and far66k reach the stepped form with 0 and exactly 1 CSR-summed slice by
+    a NumPy restatement of k_sell_span / k_sell_classify; HaloPlan gives the
+    band's reach as n_front / n_ext - n; half_values scales up, down and not at
+    all within one slice, and nothing rounds to 0 or Inf. And the SpMV and
+    prologue bounds see each variant's own defects, on the GPU cases' inputs:
+      test_halo                        test_halo_inputs (local columns off by one, halo zero / swapped)
+      test_half_values, _halo          test_half_inputs (e_i ignored, e_i+-1, the unscaled cast)
+      test_stepped                     test_stepped_inputs (base of k+-1, wrapped offsets, slice skipped)
+      test_block_jacobi_node           test_block_jacobi_inputs (not applied, block +-1, transposed)"""
+import re
+from pathlib import Path
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
 from tests import arnoldi_ref_np as R
-from tests.arnoldi_phase import CLASSES, MATRICES, ld_of
+from tests.arnoldi_phase import CLASSES, FAR66_ROW, MATRICES, RANK_SPLITS, RankBlock, front_pad, ld_of
 
 TT = {"f32": np.float32, "f64": np.float64}
 BAND_N = [260, 4099, 4100, 8197]
@@ -464,3 +478,294 @@ def test_givens_tolerance_sees_defects(t):
             assert np.max(np.abs(M["col"].astype(np.float64) - G["col"])) >= 4 * tol, name
         M = R.ref_givens(k - 1, col, None, cs, sn, s, nrm, T)
         assert abs(float(M["col"][k - 1]) - float(G["col"][k - 1])) >= 4 * tol, "k off by one"
+
+
+# ---------------------------------------------------------------- (c) the storage variants
+# tests/test_arnoldi_variants_gpu.py: the generators give what the GPU cases rely on, and the SpMV bound
+# (R.tol_spmv, R.tol_node_bj, R.tol_prologue_w0) sees the defects of each variant's own address arithmetic.
+# A mutation reaches the rows whose operands it changes; at least a quarter of them must move by 4 bounds
+# (a defect confined to one slice: a quarter of the rows it reaches there).
+def test_front_pad_restates_the_header():
+    """front_pad against MPG_FRONT_PAD as include/mpgmres/arnoldi.h defines it (the macro's text, evaluated)."""
+    text = (Path(__file__).resolve().parent.parent / "include/mpgmres/arnoldi.h").read_text()
+    m = re.search(r"#define MPG_FRONT_PAD\(n_front\) \((.*)\)\n", text)
+    cond, yes, no = re.fullmatch(r"(.*) \? (.*) : (.*)", m.group(1)).groups()
+    expr = f"({yes.replace('/', '//')}) if ({cond}) else ({no})"
+    for nf in (0, 1, 5, 63, 64, 65, 108, 128, 1000):
+        assert front_pad(nf) == eval(expr, {"n_front": nf}), (nf, expr)
+    assert front_pad(5) == 128 and front_pad(108) == 192  # the GPU cases' pads
+
+
+def sell_span(A):
+    """k_sell_span (csrc/sell.hip): min and max of col - (first row of the row's slice)."""
+    r = np.repeat(np.arange(A.nrows), np.diff(A.rowptr))
+    d = A.col.astype(np.int64) - (r & ~63)
+    return int(d.min()), int(d.max())
+
+
+def sell_bases(A):
+    """k_sell_classify: per (slice, entry index k) the min and max of col - row over the slice's rows that
+    have an entry k, base = floor((lo + hi) / 2); a slice is CSR-summed (stepped form) when some hi - base or
+    base - lo exceeds 32767. Returns (lo, hi, base, present, bad slices)."""
+    n = A.nrows
+    r = np.repeat(np.arange(n), np.diff(A.rowptr))
+    k = np.arange(A.nnz) - A.rowptr[r]
+    s, ns, width = r // 64, -(-n // 64), int(np.diff(A.rowptr).max())
+    d = A.col.astype(np.int64) - r
+    lo = np.full((ns, width), np.iinfo(np.int64).max)
+    hi = np.full((ns, width), np.iinfo(np.int64).min)
+    np.minimum.at(lo, (s, k), d)
+    np.maximum.at(hi, (s, k), d)
+    present = hi >= lo
+    base = np.where(present, (np.where(present, lo, 0) + np.where(present, hi, 0)) >> 1, 0)
+    bad = np.flatnonzero(np.any(present & ((hi - base > 32767) | (lo - base < -32767)), axis=1))
+    return lo, hi, base, present, bad
+
+
+def test_far_matrices_reach_the_stepped_form(mpg):
+    A = MATRICES["far33k"](mpg)
+    lo, hi = sell_span(A)
+    assert A.nrows == 33_280 and (lo < -32767 or hi > 32767), (lo, hi)
+    assert len(sell_bases(A)[4]) == 0
+    B = MATRICES["far66k"](mpg)
+    lo, hi = sell_span(B)
+    ns = -(-B.nrows // 64)
+    assert B.nrows == 66_048 and ns == 1032 and (lo < -32767 or hi > 32767)
+    bad = sell_bases(B)[4]
+    assert bad.tolist() == [FAR66_ROW // 64] and len(bad) * 100 <= ns
+    # element 0 of the two rows: r - 33,000 and r + 33,000
+    for row, off in ((FAR66_ROW, -33_000), (FAR66_ROW + 1, 33_000)):
+        assert B.col[B.rowptr[row]] - row == off
+    assert B.rowptr[FAR66_ROW + 2] - B.rowptr[FAR66_ROW + 1] == 1
+
+
+def test_halo_plan_of_the_band(mpg):
+    """band-ranks' three row blocks: the halo a rank needs is the band's reach below (n_front) and above
+    (n_ext - n) its rows, read from the matrix' own offsets."""
+    A = MATRICES["band-ranks"](mpg)
+    off = A.col.astype(np.int64) - np.repeat(np.arange(A.nrows), np.diff(A.rowptr))
+    below, above = int(-off.min()), int(off.max())
+    assert (below, above) == (5, 4)  # gen_band(n, 5, 4): five sub-diagonals, four super-diagonals
+    want = [(0, 4099 + above), (below, 4099 + above), (below, 4099)]
+    for rank in range(3):
+        B = RankBlock(mpg, A, RANK_SPLITS["band-ranks"], rank)
+        assert (B.n_front, B.n_ext) == want[rank], (rank, B.n_front, B.n_ext)
+        assert B.A.col.min() == -B.n_front and B.A.col.max() == B.n_ext - 1
+        # the local numbering keeps the band: local col - local row = global col - global row
+        lrow = np.repeat(np.arange(B.n), np.diff(B.A.rowptr))
+        assert np.array_equal(B.glob[B.A.col + B.n_front] - B.glob[lrow + B.n_front], B.A.col - lrow)
+    S = MATRICES["stencil-ranks"](mpg)
+    for rank, (nf, ne) in enumerate([(0, 324 + 108), (108, 324)]):  # one plane of 36 nodes, 3 dof each
+        B = RankBlock(mpg, S, RANK_SPLITS["stencil-ranks"], rank)
+        assert (B.n_front, B.n_ext) == (nf, ne)
+
+
+HALF_MATRICES = {"band-stiff": 1, "band-stiff8197": 1, "band4099": 0, "band8197": 0, "stencil5": 1}
+
+
+@pytest.mark.parametrize("name", sorted(HALF_MATRICES))
+def test_half_values_rule(mpg, name):
+    A = MATRICES[name](mpg)
+    scale = HALF_MATRICES[name]
+    bits, e, M = R.half_values(A, scale)
+    h = bits.view(np.float16)
+    assert np.all(np.isfinite(h)) and not np.any((h == 0) & (A.val != 0)), "an entry rounds to 0 or Inf"
+    rows = np.repeat(np.arange(A.nrows), np.diff(A.rowptr))
+    rmax = np.maximum.reduceat(np.abs(h.astype(np.float64)), A.rowptr[:-1])
+    assert np.all((rmax >= 2.0 ** -2) & (rmax <= 2.0 ** 15))  # (a maximum just under 2^15 may round up to it)
+    # the copy is within fp16's rounding of A, entry by entry (normal range), whatever the row's scale
+    big = np.abs(np.ldexp(A.val, e[rows])) >= 2.0 ** -14
+    assert np.all(np.abs(M.data - A.val)[big] <= 2.0 ** -11 * (1 + 2.0 ** -20) * np.abs(A.val)[big])
+    if name.startswith("band-stiff"):
+        sl = np.arange(A.nrows) // 64
+        both = [s for s in range(sl.max() + 1) if np.any(e[sl == s] > 0) and np.any(e[sl == s] < 0)
+                and np.any(e[sl == s] == 0)]
+        assert len(both) > 0 and np.count_nonzero(e) > A.nrows // 7
+    else:
+        assert not e.any()
+
+
+def moved_fraction(ref, mut, tol, reached, what, everywhere=False):
+    """At least a quarter (everywhere: all) of the rows the mutation reaches move by 4 bounds; a row that
+    turns Inf or NaN has moved."""
+    reached = np.flatnonzero(reached) if np.asarray(reached).dtype == bool else np.asarray(reached)
+    assert len(reached) > 0, (what, "reaches no row")
+    with np.errstate(invalid="ignore"):
+        moved = ~(np.abs(mut[reached] - ref[reached]) < 4 * tol[reached])
+    frac = float(np.mean(moved))
+    assert frac >= (1.0 if everywhere else 0.25), (what, frac, len(reached))
+
+
+def _rows_of(M, cols_mask):
+    """Rows of M with an entry in a masked column."""
+    return np.flatnonzero(np.diff(M.indptr) > 0) if cols_mask is None else \
+        np.unique(np.repeat(np.arange(M.shape[0]), np.diff(M.indptr))[cols_mask[M.indices]])
+
+
+def _recol(M, newcol):
+    """M with its column indices replaced (clipped into range; duplicates are summed, as a kernel would)."""
+    return sp.csr_matrix((M.data.copy(), np.clip(newcol, 0, M.shape[1] - 1), M.indptr.copy()), shape=M.shape)
+
+
+def _spmv_and_prologue(M64, Mo64, w_ext, x_ext, b, T, acc32, n_front):
+    """The two row-sum launches of a variant on a GPU case's inputs: evaluate(M, Mo, w, x) -> [(w, tol), (w0, tol)]."""
+    terms = int(np.diff(M64.indptr).max())
+
+    def evaluate(M, Mo, w, x):
+        _, ref, scale = R.ref_spmv_step(M, w, T(0.37), None, n_front)
+        P = R.ref_prologue(Mo, b, x, T, None, n_front)
+        return [(ref, R.tol_spmv(ref, scale, terms, T, acc32)), (P["w0"].astype(np.float64), R.tol_prologue_w0(P, T))]
+
+    return evaluate
+
+
+HALO_BLOCKS = [("band-ranks", 0), ("band-ranks", 1), ("band-ranks", 2), ("stencil-ranks", 0), ("stencil-ranks", 1)]
+
+
+@pytest.mark.parametrize("name,rank", HALO_BLOCKS)
+@pytest.mark.parametrize("cls", CLS)
+def test_halo_inputs(mpg, cls, name, rank):
+    """test_halo's SpMV (w_prev seed 25) and prologue (x seed 51, b seed 52): the local column index off by
+    one either way (a wrong front offset), the upper halo read as zero, the lower halo taken from the upper."""
+    T, acc32 = _cls(cls)
+    A = MATRICES[name](mpg)
+    B = RankBlock(mpg, A, RANK_SPLITS[name], rank)
+    n, nf, N = B.n, B.n_front, A.nrows
+    M64 = B.to_scipy()
+    Mo = M64.copy()
+    M64.data = M64.data.astype(T).astype(np.float64)
+    w = R.gen_vec(N, 25, 5, T)[B.glob]
+    x, b = R.gen_vec(N, 51, 2, np.float64)[B.glob], R.gen_vec(N, 52, 4, np.float64)[B.own]
+    ev = _spmv_and_prologue(M64, Mo, w, x, b, T, acc32, nf)
+    base = ev(M64, Mo, w, x)
+    allrows = np.arange(n)
+    for sh in (1, -1):
+        mut = ev(_recol(M64, M64.indices + sh), _recol(Mo, Mo.indices + sh), w, x)
+        for (r0, tol), (r1, _), what in zip(base, mut, ("spmv", "prologue")):
+            moved_fraction(r0, r1, tol, allrows, f"{what}: columns shifted by {sh}")
+    cols = np.arange(nf + B.n_ext)
+    if B.n_ext > n:
+        up = cols >= nf + n
+        wz, xz = np.where(up, 0, w).astype(T), np.where(up, 0, x)
+        for (r0, tol), (r1, _), what in zip(base, ev(M64, Mo, wz, xz), ("spmv", "prologue")):
+            moved_fraction(r0, r1, tol, _rows_of(M64, up), f"{what}: upper halo read as zero")
+    if nf and B.n_ext > n:
+        lo = cols < nf
+        src = nf + n + np.arange(nf) % (B.n_ext - n)
+        wl, xl = w.copy(), x.copy()
+        wl[:nf], xl[:nf] = w[src], x[src]
+        for (r0, tol), (r1, _), what in zip(base, ev(M64, Mo, wl, xl), ("spmv", "prologue")):
+            moved_fraction(r0, r1, tol, _rows_of(M64, lo), f"{what}: lower halo taken from the upper")
+    # x_norm over the halo as well would count rows twice across the ranks: the bound sees it
+    xn = float(np.sqrt((x[nf:nf + n] ** 2).sum()))
+    if B.n_ext > n or nf:
+        assert abs(float(np.sqrt((x ** 2).sum())) - xn) >= 4 * ((n + 2) * 2.0 ** -53 + 2.0 ** -53) * xn
+
+
+HALF_CASES = [("band-stiff", None), ("band-stiff8197", None), ("band-stiff-ranks", 1)]
+
+
+@pytest.mark.parametrize("name,rank", HALF_CASES)
+@pytest.mark.parametrize("acc32", [False, True])
+def test_half_inputs(mpg, acc32, name, rank):
+    """test_half_values / test_half_values_halo on scaled rows: e_i ignored, e_i of the neighbouring row,
+    and the fp16 values read as the unscaled cast (which overflows the rows scaled down, and loses the small
+    entries of the rows scaled up to fp16's subnormal range)."""
+    T = np.float32
+    A = MATRICES[name](mpg)
+    N, nf = A.nrows, 0
+    glob = np.arange(N)
+    if rank is not None:
+        B = RankBlock(mpg, A, RANK_SPLITS[name], rank)
+        A, nf, glob = B.A, B.n_front, B.glob
+    bits, e, M = R.half_values(A, 1, nf)
+    terms = int(np.diff(M.indptr).max())
+    w = R.gen_vec(N, 25, 5, T)[glob]
+    _, ref, scale = R.ref_spmv_step(M, w, T(0.37), None, nf)
+    tol = R.tol_spmv(ref, scale, terms, T, acc32)
+    moved_fraction(ref, np.ldexp(ref, e), tol, e != 0, "e_i ignored", everywhere=True)
+    for sh in (1, -1):
+        en = np.roll(e, sh)
+        moved_fraction(ref, np.ldexp(ref, e - en), tol, e != en, f"e_i of row i {-sh:+d}", everywhere=True)
+    with np.errstate(over="ignore"):
+        plain = A.val.astype(np.float32).astype(np.float16).astype(np.float64)
+    Mp = sp.csr_matrix((plain, M.indices.copy(), M.indptr.copy()), shape=M.shape)
+    with np.errstate(invalid="ignore", over="ignore"):
+        _, mut, _ = R.ref_spmv_step(Mp, w, T(0.37), None, nf)
+    reached = np.flatnonzero(np.add.reduceat((Mp.data != M.data).astype(np.int64), M.indptr[:-1]) > 0)
+    assert set(np.flatnonzero(e < 0)) <= set(reached)  # every row scaled down overflows
+    moved_fraction(ref, mut, tol, reached, "the unscaled cast")
+
+
+@pytest.mark.parametrize("name", ["far33k", "far66k"])
+@pytest.mark.parametrize("cls", CLS)
+def test_stepped_inputs(mpg, cls, name):
+    """test_stepped's SpMV and prologue: a stepped column is row + base(slice, k) + int16 offset. The base of
+    entry k taken from entry k - 1 or k + 1 of the slice; the CSR-summed slice decoded from its offsets
+    wrapped to int16 (reaches the two rows whose offsets leave int16: both move); that slice skipped."""
+    T, acc32 = _cls(cls)
+    A = MATRICES[name](mpg)
+    n = A.nrows
+    M64, Mo = R.csr64(A, T), R.csr64(A, np.float64)
+    w = R.gen_vec(n, 25, 5, T)
+    x, b = R.gen_vec(n, 51, 2, np.float64), R.gen_vec(n, 52, 4, np.float64)
+    ev = _spmv_and_prologue(M64, Mo, w, x, b, T, acc32, 0)
+    base0 = ev(M64, Mo, w, x)
+    lo, hi, base, present, bad = sell_bases(A)
+    r = np.repeat(np.arange(n), np.diff(A.rowptr))
+    k = np.arange(A.nnz) - A.rowptr[r]
+    s = r // 64
+    col = A.col.astype(np.int64)
+    for sh in (1, -1):
+        kk = np.clip(k + sh, 0, base.shape[1] - 1)
+        other = np.where(present[s, kk], base[s, kk], base[s, k])  # (no neighbouring element: its own base)
+        newcol = col - base[s, k] + other
+        reached = np.unique(r[np.clip(newcol, 0, n - 1) != col])
+        assert len(reached) > n // 2
+        mut = ev(_recol(M64, newcol), _recol(Mo, newcol), w, x)
+        for (r0, tol), (r1, _), what in zip(base0, mut, ("spmv", "prologue")):
+            moved_fraction(r0, r1, tol, reached, f"{what}: base of element k {sh:+d}")
+    if name == "far66k":
+        sb = int(bad[0])
+        off = col - r - base[s, k]
+        wrapped = (off + 32768) % 65536 - 32768
+        newcol = np.where(s == sb, r + base[s, k] + wrapped, col)
+        reached = np.unique(r[newcol != col])
+        assert reached.tolist() == [FAR66_ROW, FAR66_ROW + 1]
+        mut = ev(_recol(M64, newcol), _recol(Mo, newcol), w, x)
+        for (r0, tol), (r1, _), what in zip(base0, mut, ("spmv", "prologue")):
+            moved_fraction(r0, r1, tol, reached, f"{what}: wrapped offsets", everywhere=True)
+        rows = np.arange(64 * sb, 64 * sb + 64)
+        for (r0, tol), what in zip(base0, ("spmv", "prologue")):  # (the GPU test also stores NaN there first)
+            moved_fraction(r0, np.zeros(n), tol, rows, f"{what}: slice skipped", everywhere=True)
+
+
+@pytest.mark.parametrize("name", ["stencil5", "stencil5-rows"])
+@pytest.mark.parametrize("cls", CLS)
+def test_block_jacobi_inputs(mpg, cls, name):
+    """test_block_jacobi_node: the inverses not applied, those of the neighbouring block, and the 3 x 3
+    inverses transposed. stencil5's diagonal blocks are symmetric, and so are their inverses up to the
+    set-up's rounding: a transposed read is no defect there, and no bound can see it. stencil5-rows (each
+    row scaled by its own factor) has unsymmetric blocks: the transposition is asserted there."""
+    from tests.test_bjacobi_gpu import np_block_inverse
+
+    T, acc32 = _cls(cls)
+    A = MATRICES[name](mpg)
+    n = A.nrows
+    A64 = R.csr64(A, T)
+    dinv, badb = np_block_inverse(A, 3, T)
+    assert not badb.any()
+    w = R.gen_vec(n, 25, 5, T)
+    Rj = R.ref_node_bj(A64, w, T(0.37), dinv)
+    tol = R.tol_node_bj(Rj, int(np.diff(A64.indptr).max()), T, T, acc32)
+    D = dinv.reshape(-1, 3, 3)
+    plain = A64 @ Rj["v"].astype(np.float64)
+    moved_fraction(Rj["w"], plain, tol, np.arange(n), "inverses not applied")
+    muts = [("block + 1", np.roll(D, -1, axis=0)), ("block - 1", np.roll(D, 1, axis=0))]
+    if name == "stencil5":
+        assert np.all(np.abs(D - D.transpose(0, 2, 1)) <= 4 * R.unit(T) * np.abs(D).max(axis=(1, 2), keepdims=True))
+    else:
+        muts.append(("transposed", D.transpose(0, 2, 1)))
+    for what, Dm in muts:
+        mut = R.ref_node_bj(A64, w, T(0.37), np.ascontiguousarray(Dm).reshape(-1))["w"]
+        moved_fraction(Rj["w"], mut, tol, np.arange(n), f"block Jacobi: {what}")
