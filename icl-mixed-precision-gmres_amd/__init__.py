@@ -234,6 +234,11 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_engine_refresh_seconds.argtypes = [C.c_void_p]
     lib.mpg_engine_refresh_seconds.restype = C.c_double
     lib.mpg_perturb_values.argtypes = [C.c_void_p, _I64, C.c_double, C.c_uint64, C.c_void_p]
+    lib.mpg_engine_guess_depth.argtypes = [C.c_void_p, C.c_int]
+    lib.mpg_engine_guess_keep.argtypes = [C.c_void_p]
+    lib.mpg_engine_guess_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.mpg_engine_guess_store.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 # (name, argtypes) for the kernel-level C-ABI, used by the per-kernel tests
@@ -359,6 +364,11 @@ _HIP_DECLS.update({
                                  C.POINTER(_I32)], C.c_int),
     "mpg_nrm2_pair_host": ([_P, _I64, C.c_int, _P, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)],
                            C.c_int),
+    # the initial-guess store's kernels on raw device buffers (guess.hip)
+    "mpg_guess_groups": ([_I32], C.c_int),
+    "mpg_guess_dots_f64": ([_P, _I32, _I32, _I64, _P, _P, _P], C.c_int),
+    "mpg_guess_update_f64": ([_P, _I32, _I32, _I64, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "mpg_guess_scale_f64": ([_P, _I32, _P, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
 })
 
 
@@ -672,6 +682,7 @@ def run_solve(fn, args: SolveArgs, n: int, cycle_cap: int = 4096, step_cap: int 
 
 
 ARM_B_DEVICE, ARM_X0_DEVICE = 1, 2  # MPG_ARM_B_DEVICE, MPG_ARM_X0_DEVICE (solve.h)
+ARM_X0_PROJECT = 4  # MPG_ARM_X0_PROJECT
 REFRESH_VAL_DEVICE = 1  # MPG_REFRESH_VAL_DEVICE
 
 
@@ -963,7 +974,11 @@ class Engine:
 
     PHASES = {"spmv": 0, "prologue": 1, "cgs_update": 2, "dots": 3, "spmv_storage": 4}
 
-    def __init__(self, A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, _dist=None, **opts):
+    def __init__(self, A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, _dist=None,
+                 guess_depth: int = 0, **opts):
+        """guess_depth = L > 0: the engine keeps a store of its last solutions
+        (at most L directions; set_guess_depth) and solve() / rearm() accept
+        guess="project"."""
         opts.pop("engine", None)
         self._args, self._keep = make_args(A, b, x_true, engine="fused", **opts)
         self._lib = host_lib()
@@ -985,8 +1000,65 @@ class Engine:
         if st:
             raise RuntimeError(f"mpg_engine_create: {err.value.decode()}")
         self._done = False
+        self._guess_depth = 0
+        if guess_depth:
+            try:
+                self.set_guess_depth(guess_depth)
+            except Exception:
+                self.close()
+                raise
 
-    def rearm(self, b=None, x0=None, x_true=None) -> None:
+    def _guess_flag(self, guess) -> int:
+        if guess is None:
+            return 0
+        if guess != "project":
+            raise ValueError(f"guess = {guess!r} is not None or 'project'")
+        return ARM_X0_PROJECT
+
+    def set_guess_depth(self, depth: int) -> None:
+        """Allocate the initial-guess store for `depth` directions
+        (mpg_engine_guess_depth): 0 frees it, another depth empties it.
+        RuntimeError with the status: a depth outside [0, 16], a
+        row-partitioned or measured engine, modes single and single-prec."""
+        st = self._lib.mpg_engine_guess_depth(self._h, int(depth))
+        if st:
+            msg = self._lib.mpg_engine_last_error(self._h).decode(errors="replace")
+            raise RuntimeError(f"mpg_engine_guess_depth failed ({st}): {msg}")
+        self._guess_depth = int(depth)
+
+    def guess_keep(self) -> None:
+        """keep() on the iterate the engine holds (mpg_engine_guess_keep):
+        its direction joins the store unless it is already in its span."""
+        st = self._lib.mpg_engine_guess_keep(self._h)
+        if st:
+            msg = self._lib.mpg_engine_last_error(self._h).decode(errors="replace")
+            raise RuntimeError(f"mpg_engine_guess_keep failed ({st}): {msg}")
+
+    def guess_info(self) -> dict:
+        """held / depth of the store, rho0 -> rho1 of the last projection
+        (||b - A x0|| before, and as predicted after) and the seconds spent
+        in project, keep and re-imaging so far (mpg_engine_guess_info)."""
+        held, depth = C.c_int(0), C.c_int(0)
+        r0, r1, sec = C.c_double(0), C.c_double(0), C.c_double(0)
+        if self._lib.mpg_engine_guess_info(self._h, C.byref(held), C.byref(depth), C.byref(r0), C.byref(r1),
+                                           C.byref(sec)):
+            raise RuntimeError("mpg_engine_guess_info failed")
+        return {"held": held.value, "depth": depth.value, "rho0": r0.value, "rho1": r1.value,
+                "seconds": sec.value}
+
+    def guess_store(self) -> tuple:
+        """The store's held columns as (Z, Q), each an n x held float64 array
+        (mpg_engine_guess_store): Q = A Z, Q^T Q = I."""
+        n, held = self._args.n, self.guess_info()["held"]
+        Z = np.zeros((n, max(held, 1)), dtype=np.float64, order="F")
+        Q = np.zeros_like(Z, order="F")
+        got = self._lib.mpg_engine_guess_store(self._h, Z.ctypes.data, Q.ctypes.data)
+        if got < 0:
+            msg = self._lib.mpg_engine_last_error(self._h).decode(errors="replace")
+            raise RuntimeError(f"mpg_engine_guess_store failed ({got}): {msg}")
+        return Z[:, :got], Q[:, :got]
+
+    def rearm(self, b=None, x0=None, x_true=None, guess=None) -> None:
         """Start another solve on this engine (mpg_engine_rearm): a new
         right-hand side (None: keep the current one), an initial guess (None:
         zeros) and a new x_true for err_norm (host; None: none). b and x0 are
@@ -995,9 +1067,12 @@ class Engine:
         the captured graph are kept; the solve that follows has the bits of a
         new engine's. ValueError: a vector of the wrong type, length or
         device, before anything is touched. RuntimeError with the status:
-        a row-partitioned engine, or one that ran time_phase*."""
+        a row-partitioned engine, or one that ran time_phase*.
+        guess="project": the iterate starts as the least-squares guess in
+        x0 + span(the store's directions) (MPG_ARM_X0_PROJECT); an engine
+        without a guess depth refuses it."""
         n, dev = self._args.n, self._args.device
-        flags = 0
+        flags = self._guess_flag(guess)
         ptrs, keep = [], []
         for v, name, flag in ((b, "b", ARM_B_DEVICE), (x0, "x0", ARM_X0_DEVICE), (x_true, "x_true", 0)):
             if v is None:
@@ -1042,20 +1117,25 @@ class Engine:
         return float(self._lib.mpg_engine_refresh_seconds(self._h))
 
     def solve(self, b=None, x0=None, x_true=None, max_cycles: Optional[int] = None, cycle_cap: int = 4096,
-              step_cap: int = 1 << 17, values=None) -> Result:
+              step_cap: int = 1 << 17, values=None, guess=None) -> Result:
         """One solve on the live engine: re-arm if any of b, x0, x_true is
         given (rearm), run until done or for at most max_cycles restart
         cycles, and report. Without arguments it finishes the solve the engine
         is armed with (the constructor's, or the last rearm's); a finished
         solve is only reported again. values: new values of A first
         (refresh), then the re-arm (b None keeps the right-hand side), then
-        the run. gmres_seconds: the run, timed here."""
+        the run. gmres_seconds: the run, timed here. guess="project":
+        always re-arms, from the projected guess (rearm). On an engine with a
+        guess depth every solve that finishes here keeps its solution
+        (guess_keep), the first included, whether it asked for a guess or not."""
         import time
 
+        self._guess_flag(guess)
         if values is not None:
             self.refresh(values)
-        if values is not None or b is not None or x0 is not None or x_true is not None:
-            self.rearm(b, x0, x_true)
+        if values is not None or b is not None or x0 is not None or x_true is not None or guess is not None:
+            self.rearm(b, x0, x_true, guess)
+        was_done = self._done
         t0 = time.perf_counter()
         left = max_cycles
         while not self._done and (left is None or left > 0):
@@ -1066,6 +1146,8 @@ class Engine:
         dt = time.perf_counter() - t0
         res = self.report(cycle_cap, step_cap)
         res.gmres_seconds = dt
+        if self._guess_depth and self._done and not was_done:
+            self.guess_keep()
         return res
 
     def x(self, out=None):

@@ -204,6 +204,13 @@ struct FusedEngine::Impl {
     PolyRoots poly_roots{};
     bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || (nm_asked == 1 && !cheb && !poly); }
     int basis = MPG_BASIS_F32;  // the basis' storage (MPG_BASIS, read at create; mpg_arnoldi_set_basis)
+    // the initial-guess store (FusedEngine::guess_*): g_L columns of capacity,
+    // g_p held, panels of leading dimension g_ld (padded to 256 B like the
+    // basis); nothing is allocated while g_L == 0
+    int g_L = 0, g_p = 0;
+    int64_t g_ld = 0;
+    bool g_stale = false;  // refresh_values changed A: Q is no longer A Z
+    DevMem g_Z, g_Q, g_w, g_d, g_r, g_part, g_info;
     bool orthloss = false;    // LostOrthogonality: v_{k+1} stored each step, S / u below
     DevMem loss_S, loss_u;    // (m+1) x (m+1) and m+2 of T, zero-filled (IterUtil.hpp:185-191)
 
@@ -784,6 +791,7 @@ void FusedEngine::refresh_values(const double* val, int64_t nnz, int flags) {
     load_values(val, (flags & MPG_REFRESH_VAL_DEVICE) != 0);
     check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
     armed_ = false;  // ||M^-1 b|| and the first residual belong to the old matrix: rearm() must follow
+    I.g_stale = I.g_p > 0;  // the guess store's images too: the next project or keep makes them again
     refresh_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 }
 
@@ -814,6 +822,7 @@ void FusedEngine::arm(const double* b, const double* x0, const double* x_true, i
     // (the first arm finds the allocation's zeros)
     if (solves_ > 0) check(mpg_memset(ctx, I.x.p, 0, I.x.bytes), "memset", ctx);
     if (x0) put(x0, (flags & MPG_ARM_X0_DEVICE) != 0, I.xp);
+    if (flags & MPG_ARM_X0_PROJECT) guess_project(x0 != nullptr);
     I.have_xt = x_true != nullptr;
     if (x_true) {
         if (!I.xt.p) I.xt = DevMem(ctx, n8 + 8);  // (the first x_true this engine is given)
@@ -893,6 +902,10 @@ void FusedEngine::rearm(const double* b, const double* x0, const double* x_true,
                           "re-arming a row-partitioned engine is not available: the norms of the new vectors and "
                           "the halo of the initial guess would have to cross the ranks");
     if (measured) throw StatusError(MPG_ERR_UNSUPPORTED, kMeasuredText);
+    if ((flags & MPG_ARM_X0_PROJECT) && I.g_L == 0)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          "MPG_ARM_X0_PROJECT needs a guess store and this engine has none (depth 0): "
+                          "mpg_engine_guess_depth comes first");
     auto t0 = clk::now();
     arm(b, x0, x_true, flags);
     check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
@@ -913,6 +926,171 @@ void FusedEngine::copy_x(double* dst, bool dst_on_device) {
             from = I.stage64.p;
         }
         check(mpg_memcpy_d2h(I.ctx, dst, from, n8), "d2h", I.ctx);
+    }
+    sync();
+}
+
+// ---------------------------------------------------------------- the initial-guess store
+//  Z and Q = A Z with Q^T Q = I, fp64, A = val_outer on csr: the
+// matrix of the residual prologue. project: the least-squares guess in
+// xbar + span Z; keep: the newest solution orthogonalised in by two passes of
+// classical Gram-Schmidt on the images. Launches: project = dots + update
+// (+ the SpMV of b - A xbar where xbar != 0); keep = SpMV, dots, two update
+// passes, scale.
+void FusedEngine::guess_check(const char* what) const {
+    const Impl& I = *p_;
+    const std::string w = std::string(what) + ": the guess store ";
+    if (I.comm)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          w + "is not available on a row-partitioned engine: Q^T r and the norms would have to "
+                              "cross the ranks, and the re-arm that projects is not available there either");
+    if (measured) throw StatusError(MPG_ERR_UNSUPPORTED, w + "is not available: " + kMeasuredText);
+    if (I.ty.X != MPG_F64)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          w + "is not available in the modes whose outer type is fp32 (single): solutions "
+                              "resolved to 1e-7 cannot make guesses worth a cycle");
+    if (I.args.mode == MPG_MODE_SINGLE_PREC)
+        throw StatusError(MPG_ERR_UNSUPPORTED,
+                          w + "is not available in mode single-prec: its fp32 preconditioner bounds what the "
+                              "solves resolve, and the store is not tested there");
+}
+
+int FusedEngine::guess_held() const { return p_->g_p; }
+int FusedEngine::guess_L() const { return p_->g_L; }
+
+void FusedEngine::guess_depth(int L) {
+    Impl& I = *p_;
+    if (L < 0 || L > MPG_GUESS_MAX_DEPTH)
+        throw StatusError(MPG_ERR_ARG, "mpg_engine_guess_depth: depth " + std::to_string(L) + " is outside [0, " +
+                                           std::to_string(MPG_GUESS_MAX_DEPTH) + "]");
+    if (L > 0) guess_check("mpg_engine_guess_depth");
+    if (L == I.g_L) return;
+    check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
+    I.g_Z = DevMem(), I.g_Q = DevMem(), I.g_w = DevMem(), I.g_d = DevMem(), I.g_r = DevMem();
+    I.g_part = DevMem(), I.g_info = DevMem();
+    I.g_L = I.g_p = 0;
+    I.g_stale = false;
+    guess_rho0 = guess_rho1 = 0;
+    if (L == 0) return;
+    const int G = mpg_guess_groups(I.n);
+    if (G < 1) throw StatusError(MPG_ERR_ARG, "mpg_engine_guess_depth: an engine without rows");
+    I.g_ld = ((int64_t)I.n + 31) / 32 * 32;
+    const size_t col = (size_t)I.g_ld * 8;
+    I.g_Z = DevMem(I.ctx, col * L);
+    I.g_Q = DevMem(I.ctx, col * L);
+    I.g_w = DevMem(I.ctx, col);
+    I.g_d = DevMem(I.ctx, col);
+    I.g_r = DevMem(I.ctx, col);
+    I.g_part = DevMem(I.ctx, (size_t)3 * (L + 1) * G * 8);
+    I.g_info = DevMem(I.ctx, 64 * 8);
+    I.g_L = L;
+}
+
+void FusedEngine::guess_project(bool have_base) {
+    Impl& I = *p_;
+    const mpg_ctx_t ctx = I.ctx;
+    auto t0 = clk::now();
+    if (I.g_stale) guess_reimage();
+    const int n = I.n, p = I.g_p;
+    const double* r = I.b.as<double>();
+    if (have_base) {  // r = b - A xbar
+        check(mpg_memcpy_d2d(ctx, I.g_r.p, I.b.p, (size_t)n * 8), "d2d", ctx);
+        check(mpg_csr_spmv_f64(ctx, I.csr, -1.0, static_cast<const double*>(I.val_outer),
+                               static_cast<const double*>(I.xp), 1.0, I.g_r.as<double>()),
+              "guess residual", ctx);
+        r = I.g_r.as<double>();
+    }
+    if (p == 0) {
+        guess_rho0 = guess_rho1 = I.nrm2(r, MPG_F64, n);
+    } else {
+        double* part = I.g_part.as<double>();
+        double* coef = I.g_info.as<double>();
+        check(mpg_guess_dots_f64(ctx, n, p, I.g_ld, I.g_Q.as<double>(), r, part), "mpg_guess_dots_f64", ctx);
+        check(mpg_guess_update_f64(ctx, n, p, I.g_ld, part, 1.0, I.g_Z.as<double>(), static_cast<const double*>(I.xp),
+                                   static_cast<double*>(I.xp), nullptr, nullptr, nullptr, coef),
+              "mpg_guess_update_f64", ctx);
+        double h[MPG_GUESS_MAX_DEPTH + 1];
+        check(mpg_memcpy_d2h(ctx, h, coef, (size_t)(p + 1) * 8), "d2h", ctx);
+        double cc = 0;
+        for (int j = 0; j < p; ++j) cc += h[j] * h[j];
+        guess_rho0 = std::sqrt(h[p]);
+        guess_rho1 = std::sqrt(std::max(0.0, h[p] - cc));
+    }
+    check(mpg_ctx_sync(ctx), "sync", ctx);
+    guess_seconds += std::chrono::duration<double>(clk::now() - t0).count();
+}
+
+void FusedEngine::guess_keep_vec(const double* x) {
+    Impl& I = *p_;
+    const mpg_ctx_t ctx = I.ctx;
+    const int n = I.n;
+    if (I.g_p == I.g_L) I.g_p = 0;  // Fischer's restart: the newest solution alone reseeds the store
+    const int p = I.g_p;
+    const int G = mpg_guess_groups(n);
+    const int64_t ld = I.g_ld;
+    double *Z = I.g_Z.as<double>(), *Q = I.g_Q.as<double>(), *w = I.g_w.as<double>(), *d = I.g_d.as<double>();
+    double* pa = I.g_part.as<double>();
+    double* pb = pa + (size_t)(I.g_L + 1) * G;
+    double* pc = pb + (size_t)(I.g_L + 1) * G;
+    double* info = I.g_info.as<double>() + 32;
+    check(mpg_csr_spmv_f64(ctx, I.csr, 1.0, static_cast<const double*>(I.val_outer), x, 0.0, w), "guess image", ctx);
+    check(mpg_guess_dots_f64(ctx, n, p, ld, Q, w, pa), "mpg_guess_dots_f64", ctx);  // Q^T w, omega^2
+    const double* dv = x;
+    const double* nu2 = pa + (size_t)p * G;
+    if (p > 0) {
+        check(mpg_guess_update_f64(ctx, n, p, ld, pa, -1.0, Z, x, d, Q, w, pb, nullptr), "mpg_guess_update_f64", ctx);
+        check(mpg_guess_update_f64(ctx, n, p, ld, pb, -1.0, Z, d, d, Q, w, pc, nullptr), "mpg_guess_update_f64", ctx);
+        dv = d;
+        nu2 = pc + (size_t)p * G;
+    }
+    const double thr = std::max(I.args.tol, (double)n * 0x1p-53);
+    check(mpg_guess_scale_f64(ctx, n, nu2, pa + (size_t)p * G, thr, w, dv, Q + (size_t)p * ld, Z + (size_t)p * ld,
+                              info),
+          "mpg_guess_scale_f64", ctx);
+    double h[3] = {0, 0, 0};
+    check(mpg_memcpy_d2h(ctx, h, info, sizeof h), "d2h", ctx);
+    if (h[2] != 0.0) I.g_p = p + 1;
+}
+
+void FusedEngine::guess_reimage() {
+    Impl& I = *p_;
+    const int p = I.g_p;
+    I.g_stale = false;
+    if (p == 0) return;
+    const size_t col = (size_t)I.g_ld * 8;
+    DevMem old(I.ctx, col * p);
+    check(mpg_memcpy_d2d(I.ctx, old.p, I.g_Z.p, col * p), "d2d", I.ctx);
+    I.g_p = 0;
+    for (int j = 0; j < p; ++j) guess_keep_vec(old.as<double>() + (size_t)j * I.g_ld);
+    check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
+}
+
+void FusedEngine::guess_keep() {
+    Impl& I = *p_;
+    guess_check("mpg_engine_guess_keep");
+    if (I.g_L == 0)
+        throw StatusError(MPG_ERR_UNSUPPORTED, "mpg_engine_guess_keep: this engine has no guess store (depth 0): "
+                                               "mpg_engine_guess_depth comes first");
+    auto t0 = clk::now();
+    check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
+    if (I.g_stale) guess_reimage();
+    guess_keep_vec(static_cast<const double*>(I.xp));
+    check(mpg_ctx_sync(I.ctx), "sync", I.ctx);
+    guess_seconds += std::chrono::duration<double>(clk::now() - t0).count();
+}
+
+void FusedEngine::guess_store(double* Z, double* Q) {
+    Impl& I = *p_;
+    guess_check("mpg_engine_guess_store");
+    if (I.g_stale) {
+        auto t0 = clk::now();
+        guess_reimage();
+        guess_seconds += std::chrono::duration<double>(clk::now() - t0).count();
+    }
+    const size_t n8 = (size_t)I.n * 8;
+    for (int j = 0; j < I.g_p; ++j) {
+        if (Z) check(mpg_memcpy_d2h(I.ctx, Z + (size_t)j * I.n, I.g_Z.as<double>() + (size_t)j * I.g_ld, n8), "d2h", I.ctx);
+        if (Q) check(mpg_memcpy_d2h(I.ctx, Q + (size_t)j * I.n, I.g_Q.as<double>() + (size_t)j * I.g_ld, n8), "d2h", I.ctx);
     }
     sync();
 }
@@ -1503,6 +1681,40 @@ int mpg_engine_refresh_values(mpg_engine_t e, const double* val, int64_t nnz, in
         e->last_error = e->dead_error;
     }
     return st;
+}
+
+int mpg_engine_guess_depth(mpg_engine_t e, int depth) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return mpg::engine_call(e, [&] {
+        e->eng->guess_depth(depth);
+        return (int)MPG_OK;
+    });
+}
+
+int mpg_engine_guess_keep(mpg_engine_t e) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return mpg::engine_call(e, [&] {
+        e->eng->guess_keep();
+        return (int)MPG_OK;
+    });
+}
+
+int mpg_engine_guess_info(mpg_engine_t e, int* held, int* depth, double* rho0, double* rho1, double* seconds) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    if (held) *held = e->eng->guess_held();
+    if (depth) *depth = e->eng->guess_L();
+    if (rho0) *rho0 = e->eng->guess_rho0;
+    if (rho1) *rho1 = e->eng->guess_rho1;
+    if (seconds) *seconds = e->eng->guess_seconds;
+    return MPG_OK;
+}
+
+int mpg_engine_guess_store(mpg_engine_t e, double* Z, double* Q) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return mpg::engine_call(e, [&] {
+        e->eng->guess_store(Z, Q);
+        return e->eng->guess_held();
+    });
 }
 
 double mpg_engine_refresh_seconds(mpg_engine_t e) { return e && e->eng ? e->eng->refresh_seconds : -1.0; }

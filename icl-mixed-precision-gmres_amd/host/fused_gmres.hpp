@@ -177,6 +177,19 @@ public:
     double refresh_seconds = 0;  // the last refresh_values, wall clock (0: none yet)
     // rows [0, n) of x widened to fp64 into dst (host, or the engine's device); synchronises
     void copy_x(double* dst, bool dst_on_device);
+    // ---- the initial-guess store (mpg_engine_guess_*, solve.h) ----
+    // fp64 panels Z, Q = A Z with Q^T Q = I of the last few solutions, A the
+    // residual prologue's matrix. Off (depth 0) until guess_depth(L) allocates
+    // it: no buffer and no launch otherwise. Every entry point is refused
+    // (MPG_ERR_UNSUPPORTED) on a row-partitioned engine, after measurement
+    // launches and in the modes whose outer type is fp32.
+    void guess_depth(int L);  // 0 frees the store; another L empties it
+    void guess_keep();        // keep() on the x the engine holds
+    void guess_store(double* Z, double* Q);  // the held columns to host, n x held each, column-major, ld = n
+    int guess_held() const;
+    int guess_L() const;
+    double guess_rho0 = 0, guess_rho1 = 0;  // the last projection: ||b - A xbar|| and the predicted ||b - A x0||
+    double guess_seconds = 0;               // wall clock of every project, keep and re-imaging so far
     int solves() const { return solves_; }                  // arms so far, the constructor's included
     int graph_captures() const { return graph_captures_; }  // cycle graphs captured so far
 
@@ -229,6 +242,10 @@ private:
     // what depends on b and x: the constructor's and rearm's one code path
     void arm(const double* b, const double* x0, const double* x_true, int flags);
     void start();  // the first residual prologue of a solve and its report
+    void guess_check(const char* what) const;  // the refusals of the guess store's entry points
+    void guess_project(bool have_base);        // x <- x + Z Q^T (b - A x) (arm, MPG_ARM_X0_PROJECT)
+    void guess_keep_vec(const double* x_dev);  // keep() on a device vector of n
+    void guess_reimage();                      // after refresh_values: Q = A Z again, column by column
     void prologue();
     void step(int k, bool fold);
     void issue(const Op& op);

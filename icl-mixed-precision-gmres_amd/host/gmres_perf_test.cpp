@@ -36,7 +36,14 @@
 // solve through mpg_solve as before), --vary-values EPS (with --solves N > 1:
 // system j >= 1 has the matrix mpg_perturb_values(A, EPS, seed = j) on A's
 // pattern and b_j = A_j x_true, given to the engine by
-// mpg_engine_refresh_values before the re-arm; the stdout block is unchanged).
+// mpg_engine_refresh_values before the re-arm; the stdout block is unchanged),
+// --guess project [--guess-depth L] (with --solves N > 1: the engine keeps a
+// store of its last solutions, at most L directions, default 8, and system
+// j >= 1 starts from the least-squares guess in their span:
+// mpg_engine_guess_depth, MPG_ARM_X0_PROJECT, mpg_engine_guess_keep; the stdout
+// block is unchanged and the guess's residual norms go to stderr), --rhs-path K
+// (x_true of system j is sum_{k < K} cos(0.37 (k + 1) j + k) rand_vect(--rand + k):
+// the solutions of a sequence move in a K-dimensional space; not with --bpath).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -79,6 +86,9 @@ int main(int argc, char* argv[]) {
     int solves = 1;
     bool vary = false;  // --vary-values
     double vary_eps = 0.0;
+    bool guess = false;    // --guess project
+    int guess_depth = 8;   // --guess-depth
+    int rhs_path = 0;      // --rhs-path (0: x_true = rand_vect(--rand + j))
 
     for (int i = 1; i < argc; ++i) {
         const std::string f = argv[i];
@@ -112,6 +122,13 @@ int main(int argc, char* argv[]) {
             vary = true;
             vary_eps = std::stod(next());
         }
+        else if (f == "--guess") {
+            const std::string v = next();
+            if (v != "project") { std::cout << "Unknown guess (project)" << std::endl; return 1; }
+            guess = true;
+        }
+        else if (f == "--guess-depth") guess_depth = std::stoi(next());
+        else if (f == "--rhs-path") rhs_path = std::stoi(next());
         else if (f == "--half-unscaled") a.half_unscaled = 1;
         else if (f == "--stop-on-breakdown") a.stop_on_breakdown = 1;
         else if (f == "--accum") {  // fp32 Arnoldi's accumulation class (solve.h)
@@ -184,6 +201,14 @@ int main(int argc, char* argv[]) {
         std::cout << "--vary-values forms b_j = A_j x_true itself and cannot take --bpath" << std::endl;
         return 1;
     }
+    if (guess && solves < 2) {
+        std::cout << "--guess project starts the systems of --solves N, N > 1, from the earlier solutions" << std::endl;
+        return 1;
+    }
+    if (rhs_path < 0 || (rhs_path > 0 && b_path)) {
+        std::cout << "--rhs-path takes a positive number of directions and forms x_true itself (no --bpath)" << std::endl;
+        return 1;
+    }
     if (solves > 1 && (a.engine != MPG_ENGINE_FUSED || ngpus >= 1)) {
         // (the library's rule: mpg_engine_rearm exists on the fused engine, on one GPU)
         std::cerr << "mpg_solve failed: mpgmres: a sequence of solves on one engine (--solves) runs on the fused "
@@ -210,8 +235,22 @@ int main(int argc, char* argv[]) {
     }
     const int64_t n = A.nrows;
     std::vector<double> x_true((size_t)n), b((size_t)n);
+    // x_true of system j: rand_vect(--rand + j), or the point j of --rhs-path's curve
+    std::vector<std::vector<double>> path_dirs((size_t)rhs_path, std::vector<double>((size_t)n));
+    for (int k = 0; k < rhs_path; ++k) mpg_rand_vect(n, rand_seed + (unsigned)k, path_dirs[(size_t)k].data());
+    auto make_x_true = [&](int j) {
+        if (rhs_path == 0) {
+            mpg_rand_vect(n, rand_seed + (unsigned)j, x_true.data());
+            return;
+        }
+        std::fill(x_true.begin(), x_true.end(), 0.0);
+        for (int k = 0; k < rhs_path; ++k) {
+            const double c = std::cos(0.37 * (k + 1) * j + k);
+            for (int64_t i = 0; i < n; ++i) x_true[(size_t)i] += c * path_dirs[(size_t)k][(size_t)i];
+        }
+    };
     if (!b_path) {
-        mpg_rand_vect(n, rand_seed, x_true.data());
+        make_x_true(0);
         mpg_host_spmv(&A, x_true.data(), b.data());
     } else {
         std::fill(x_true.begin(), x_true.end(), 0.0);
@@ -248,7 +287,7 @@ int main(int argc, char* argv[]) {
                 // --vary-values: system j's matrix, the first one's values perturbed with seed j
                 if (vary) mpg_perturb_values(val0.data(), A.nnz, vary_eps, (uint64_t)j, A.val);
                 if (!b_path) {
-                    mpg_rand_vect(n, rand_seed + (unsigned)j, x_true.data());
+                    make_x_true(j);
                     mpg_host_spmv(&A, x_true.data(), b.data());
                 }
                 print_norms();
@@ -256,9 +295,11 @@ int main(int argc, char* argv[]) {
             std::cout << banner << std::endl;
             if (j == 0) {
                 st = mpg_engine_create(&a, &eng, r.message, (int)sizeof r.message);
+                if (st == 0 && guess && (st = mpg_engine_guess_depth(eng, guess_depth)) != 0)
+                    std::snprintf(r.message, sizeof r.message, "%s", mpg_engine_last_error(eng));
             } else {
                 if (vary) st = mpg_engine_refresh_values(eng, A.val, A.nnz, 0);
-                if (st == 0) st = mpg_engine_rearm(eng, b.data(), nullptr, x_true.data(), 0);
+                if (st == 0) st = mpg_engine_rearm(eng, b.data(), nullptr, x_true.data(), guess ? MPG_ARM_X0_PROJECT : 0);
                 if (st != 0) std::snprintf(r.message, sizeof r.message, "%s", mpg_engine_last_error(eng));
             }
             if (st != 0) break;
@@ -279,6 +320,17 @@ int main(int argc, char* argv[]) {
             if (st != 0) break;
             std::cout << "  ilu took " << (float)r.setup_seconds << "s; gmres took " << (float)gmres_s << "s" << std::endl;
             std::cout << "  resNorm = " << r.res_norm << "; errNorm = " << r.err_norm << std::endl;
+            if (guess) {
+                // (stderr: the stdout block stays the reference's)
+                int held = 0, depth = 0;
+                double rho0 = 0, rho1 = 0, secs = 0;
+                mpg_engine_guess_info(eng, &held, &depth, &rho0, &rho1, &secs);
+                if (j > 0)
+                    std::cerr << "guess: system " << j << ": ||b - A x0|| " << rho0 << " -> " << rho1 << " from " << held
+                              << " of " << depth << " directions" << std::endl;
+                st = mpg_engine_guess_keep(eng);
+                if (st != 0) std::snprintf(r.message, sizeof r.message, "%s", mpg_engine_last_error(eng));
+            }
         }
         mpg_engine_destroy(eng);
     } else if (ngpus >= 1 && !(ngpus == 1 && a.engine != MPG_ENGINE_FUSED)) {

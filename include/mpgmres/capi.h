@@ -547,6 +547,34 @@ int mpg_sell_poly_sweep_f64(mpg_ctx_t ctx, mpg_sell_t A, const double* dinv, con
 int mpg_sell_poly_sweep_f32(mpg_ctx_t ctx, mpg_sell_t A, const float* dinv, const float* g, const float* p, float* z,
                             float* out, int32_t form, int32_t first, int32_t last, float c0, float c1);
 
+/* ---- the initial-guess store's kernels (an addition to the reference's set; mpg_engine_guess_*, solve.h) ----
+ * fp64 throughout. A panel is column-major with leading dimension ld >= n, ld even, its base 16-byte aligned, and
+ * holds nc <= MPG_GUESS_MAX_DEPTH columns; every vector is 16-byte aligned. Sums are two-stage and deterministic:
+ * G = mpg_guess_groups(n) workgroups store one fp64 partial per column, partial[c * G + g], and the consumer adds
+ * them in one fixed order (no atomics, no reduce launch). Nothing at or past row n is read or written. Each call is
+ * one launch on ctx's stream; MPG_ERR_ARG for anything outside the above. */
+#define MPG_GUESS_MAX_DEPTH 16
+/* workgroups (= partials per column) of the launches below for n rows; MPG_ERR_ARG for n < 1 */
+int mpg_guess_groups(int32_t n);
+/* partial columns 0 .. nc-1 = Q^T r, column nc = ||r||^2; partial holds (nc + 1) * G doubles. nc == 0: the norm alone
+ * (Q may be NULL) */
+int mpg_guess_dots_f64(mpg_ctx_t ctx, int32_t n, int32_t nc, int64_t ld, const double* Q, const double* r,
+                       double* partial);
+/* c = the sums of partial's columns 0 .. nc (mpg_guess_dots_f64's, or this call's partial_out), 1 <= nc;
+ * y = y_in + alpha Z c over rows [0, n): row i is y_in[i], then fma(Z(i, j), alpha c_j, .) for j = 0 .. nc-1 in order
+ * (y_in NULL: zeros; y_in == y: in place). With the second pair (Q, w, partial_out all non-NULL, else all NULL) the
+ * same launch does w = w + alpha Q c likewise and stores the partials of Q^T w' and ||w'||^2 of the new w in
+ * partial_out ((nc + 1) * G doubles, not `partial`): one pass of classical Gram-Schmidt on a vector and its
+ * pre-image with alpha = -1, the next pass' dots included. coef_out (may be NULL): the nc + 1 sums used. */
+int mpg_guess_update_f64(mpg_ctx_t ctx, int32_t n, int32_t nc, int64_t ld, const double* partial, double alpha,
+                         const double* Z, const double* y_in, double* y, const double* Q, double* w,
+                         double* partial_out, double* coef_out);
+/* The update's final form: nu = sqrt(sum of nu2_partial[0 .. G)), omega = sqrt(sum of om2_partial[0 .. G)); where both
+ * are finite and nu > thr * omega, qcol = w / nu and zcol = d / nu over rows [0, n); info[0 .. 3) = nu, omega, and 1.0
+ * where the columns were stored, else 0.0 (device memory). */
+int mpg_guess_scale_f64(mpg_ctx_t ctx, int32_t n, const double* nu2_partial, const double* om2_partial, double thr,
+                        const double* w, const double* d, double* qcol, double* zcol, double* info);
+
 #ifdef __cplusplus
 }
 #endif

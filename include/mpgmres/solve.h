@@ -175,7 +175,37 @@ const char* mpg_engine_last_error(mpg_engine_t e);
  * measurement launches (mpg_engine_time_*; mpg_engine_run's rule and text). */
 #define MPG_ARM_B_DEVICE 1
 #define MPG_ARM_X0_DEVICE 2
+/* the initial guess is projected from the engine's guess store (below): x starts as project(b, x0) */
+#define MPG_ARM_X0_PROJECT 4
 int mpg_engine_rearm(mpg_engine_t e, const double* b, const double* x0, const double* x_true, int flags);
+/* ---- the initial guess projected from earlier solutions (an addition to the reference's set) ----
+ * An engine with guess depth L, 1 <= L <= MPG_GUESS_MAX_DEPTH (16, capi.h), owns two fp64 column-major panels Z and Q
+ * of n x L on the device and a count held <= L, with Q(:, j) = A Z(:, j) and Q^T Q = I; A is the matrix of the
+ * residual prologue (the fp64 A; in mode baseline double(float(A))).
+ *   project(b, xbar): r = b - A xbar (one mpg_csr_spmv_f64, skipped for xbar = 0), c = Q^T r, x0 = xbar + Z c:
+ *     ||b - A x0|| = ||(I - Q Q^T) r|| is the least over xbar + span Z and never above ||r||. rho0 = ||r||, and the
+ *     predicted rho1 = sqrt(max(0, ||r||^2 - ||c||^2)). Two launches (mpg_guess_dots_f64, mpg_guess_update_f64).
+ *   keep(x): w = A x, d = x, omega = ||w||; classical Gram-Schmidt twice (h = Q^T w, w -= Q h, d -= Z h); nu = ||w||;
+ *     unless nu or omega is not finite or nu <= max(tol, n 2^-53) omega (a direction below what the solves resolve),
+ *     Q(:, held) = w / nu, Z(:, held) = d / nu, held += 1. With held == L on entry, held = 0 first (Fischer's restart:
+ *     the newest solution alone reseeds the store). The SpMV and four launches. Allowed whatever the solve's status.
+ *   after mpg_engine_refresh_values the images are stale: the next project, keep or store read first keeps the held
+ *     Z columns again, in order, from an empty store (held SpMVs and their orthogonalisation; counted in the guess
+ *     store's seconds, not in mpg_engine_refresh_seconds).
+ * mpg_engine_guess_depth allocates the store (L = 0 frees it; another L empties it; the same L is a no-op). With
+ * MPG_ARM_X0_PROJECT in mpg_engine_rearm's flags the re-arm writes project(b, x0) where it writes x0 (x0 NULL: zeros).
+ * mpg_engine_guess_keep runs keep() on the x the engine holds. mpg_engine_guess_info reads the count, the depth, rho0
+ * and rho1 of the last projection and the wall-clock seconds of every project, keep and re-imaging so far (any
+ * pointer may be NULL). mpg_engine_guess_store copies the held columns to host (n x held each, column-major, leading
+ * dimension n; either may be NULL) and returns held. Without a depth nothing is allocated and no launch is made.
+ * MPG_ERR_UNSUPPORTED with the reason in mpg_engine_last_error, the engine left usable: a row-partitioned engine; an
+ * engine that ran measurement launches; modes single and single-prec (an fp32 outer type or preconditioner bounds
+ * the solves near 1e-7: no guess worth a cycle); MPG_ARM_X0_PROJECT or mpg_engine_guess_keep without a depth.
+ * MPG_ERR_ARG: e is NULL, or L outside [0, 16]. */
+int mpg_engine_guess_depth(mpg_engine_t e, int depth);
+int mpg_engine_guess_keep(mpg_engine_t e);
+int mpg_engine_guess_info(mpg_engine_t e, int* held, int* depth, double* rho0, double* rho1, double* seconds);
+int mpg_engine_guess_store(mpg_engine_t e, double* Z, double* Q);
 /* ---- new matrix values on the unchanged sparsity pattern (Newton steps, time steps, parameter sweeps) ----
  * mpg_engine_refresh_values gives a live engine a new A with the pattern it was created with: val holds nnz fp64
  * values in CSR order, in host memory or, with MPG_REFRESH_VAL_DEVICE in `flags`, in the memory of the engine's
