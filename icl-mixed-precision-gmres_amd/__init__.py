@@ -213,6 +213,7 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.mpg_cycle_plan_describe.argtypes = [C.POINTER(CyclePolicy), C.c_char_p, C.c_int]
     lib.mpg_engine_accum.argtypes = [C.c_void_p]
     lib.mpg_engine_basis.argtypes = [C.c_void_p]
+    lib.mpg_engine_prec_values.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_fused.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_sweeps.argtypes = [C.c_void_p]
     lib.mpg_engine_prec_interval.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -332,6 +333,14 @@ _HIP_DECLS.update({
     "mpg_csr_poly_sweep_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, C.c_float], C.c_int),
     "mpg_sell_poly_sweep_f64": ([_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_double, C.c_double], C.c_int),
     "mpg_sell_poly_sweep_f32": ([_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, C.c_float], C.c_int),
+    "mpg_csr_jacobi_sweep_f16f32": ([_P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "mpg_sell_jacobi_sweep_f16f32": ([_P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "mpg_csr_cheb_sweep_f16f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float], C.c_int),
+    "mpg_sell_cheb_sweep_f16f32": ([_P, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float], C.c_int),
+    "mpg_csr_poly_sweep_f16f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, C.c_float],
+                                  C.c_int),
+    "mpg_sell_poly_sweep_f16f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, C.c_float], C.c_int),
+    "mpg_csr_half_dequant_f32": ([_P, _P, _P, _P, _P, C.POINTER(_I64)], C.c_int),
     "mpg_arnoldi_poly_apply": ([_P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P], C.c_int),
     "mpg_gmres_poly_roots": ([C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                               C.POINTER(C.c_int)], C.c_int),
@@ -339,6 +348,8 @@ _HIP_DECLS.update({
     "mpg_arnoldi_destroy": ([_P], C.c_int),
     "mpg_arnoldi_set_accum": ([_P, C.c_int], C.c_int),
     "mpg_arnoldi_set_basis": ([_P, C.c_int], C.c_int),
+    "mpg_arnoldi_set_prec_copy": ([_P, _I32, _P, _P, _P], C.c_int),
+    "mpg_arnoldi_prec_values": ([_P], C.c_int),
     "mpg_arnoldi_basis": ([_P], C.c_int),
     "mpg_arnoldi_basis_dev": ([_P, C.POINTER(_I64)], _P),
     "mpg_arnoldi_givens_spmv": ([_P, C.c_int], C.c_int),
@@ -599,7 +610,7 @@ def make_args(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, mod
               prec="identity", rlen=30, tol=1e-6, max_restarts=1_000_000, rtol=0.0, repeat_iter=False,
               orthloss=False, jacobi_steps=1, engine="fused", verbose=False, device=0, threads=0,
               spmv_format="auto", half_unscaled=False, stop_on_breakdown=False, accum="f64", prec_block=3,
-              basis=None):
+              basis=None, prec_values=None):
     """Build mpg_solve_args (shared by mpg_solve and the CPU oracle).
     accum: the fp32 Arnoldi's accumulation class, "f64" (fp32 products
     summed in fp64, rounded once) or "f32" (every partial sum in fp32: the
@@ -611,7 +622,13 @@ def make_args(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, mod
     as fp32; tests). Not a field of mpg_solve_args: it rides on the returned
     structure and the call that creates the engine runs with the setting
     MPG_BASIS in its place (mpg_engine_basis, solve.h), restored afterwards.
-    None: the process's own MPG_BASIS, f32 when unset."""
+    None: the process's own MPG_BASIS, f32 when unset.
+    prec_values: the matrix values the sweeps of prec="neumann" (two steps or
+    more), "chebyshev" and "gmres_poly" read: "f32" (the Arnoldi matrix),
+    "f16" (an fp16 copy of A with int8 row exponents: 2 bytes per value; mode
+    mixed, one GPU) or "f16emu" (the same values held as fp32, CSR storage;
+    tests). Delivered like `basis`, through the setting MPG_PREC_VALUES
+    (mpg_engine_prec_values, solve.h). None: the process's own, f32 when unset."""
     b = np.ascontiguousarray(b, dtype=np.float64)
     keep = [A.rowptr, A.col, A.val, b]
     a = SolveArgs()
@@ -634,27 +651,33 @@ def make_args(A: Csr, b: np.ndarray, x_true: Optional[np.ndarray] = None, *, mod
     a.accum = ACCUMS[accum]
     a.prec_block = prec_block
     a._basis = None if basis is None else str(basis)
+    a._prec_values = None if prec_values is None else str(prec_values)
     return a, keep
 
 
 class _basis_setting:
-    """MPG_BASIS = args' basis around the call that creates an engine (the
-    setting is read once there); the process's own value is put back."""
+    """MPG_BASIS = args' basis and MPG_PREC_VALUES = args' prec_values around
+    the call that creates an engine (the settings are read once there); the
+    process's own values are put back."""
 
     def __init__(self, args):
         self.basis = getattr(args, "_basis", None)
+        self.set = {"MPG_BASIS": self.basis, "MPG_PREC_VALUES": getattr(args, "_prec_values", None)}
+        self.old = {}
 
     def __enter__(self):
-        if self.basis is not None:
-            self.old = os.environ.get("MPG_BASIS")
-            os.environ["MPG_BASIS"] = self.basis
+        for name, value in self.set.items():
+            if value is not None:
+                self.old[name] = os.environ.get(name)
+                os.environ[name] = value
 
     def __exit__(self, *exc):
-        if self.basis is not None:
-            if self.old is None:
-                os.environ.pop("MPG_BASIS", None)
+        for name, old in self.old.items():
+            if old is None:
+                os.environ.pop(name, None)
             else:
-                os.environ["MPG_BASIS"] = self.old
+                os.environ[name] = old
+        self.old = {}
         return False
 
 
@@ -1300,7 +1323,9 @@ class Engine:
         (mpg_engine_prec_roots). "basis" (mpg_engine_basis) is "f16" or
         "f16emu" under a compressed or emulated Krylov basis; like the other
         optional entries it is not listed for the default, where looking it
-        up gives "f32"."""
+        up gives "f32". "prec_values" (mpg_engine_prec_values) is "f16" or
+        "f16emu" where the sweeps read an fp16 copy of A, and is not listed
+        otherwise."""
         f, w, cb, st, win = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         if self._lib.mpg_engine_spmv_layout(self._h, C.byref(f), C.byref(w), C.byref(cb), C.byref(st), C.byref(win)):
             raise RuntimeError("mpg_engine_spmv_layout failed")
@@ -1315,6 +1340,7 @@ class Engine:
         rider = int(self._lib.mpg_engine_givens_rider(self._h)) == 1
         tail = int(self._lib.mpg_engine_tail_fold(self._h)) == 1
         basis = int(self._lib.mpg_engine_basis(self._h))
+        pv = int(self._lib.mpg_engine_prec_values(self._h))
         return _Layout({**({"dots_fused": fused} if fused > 0 else {}), **({"givens_rider": True} if rider else {}),
                 **({"tail_fold": True} if tail else {}),
                 **({"cgs_stream": stream} if stream > 0 else {}), "format": {1: "csr", 2: "sell", 3: "node"}[f.value], "vec_width": w.value, "col_bytes": cb.value,
@@ -1323,6 +1349,7 @@ class Engine:
                 "givens_folded": bool(self._lib.mpg_engine_givens_folded(self._h) == 1),
                 "accum": {0: "f64", 1: "f32"}[int(self._lib.mpg_engine_accum(self._h))],
                 **({"basis": {1: "f16", 2: "f16emu"}[basis]} if basis else {}),
+                **({"prec_values": {1: "f16", 2: "f16emu"}[pv]} if pv > 0 else {}),
                 **({"prec_fused": pf} if pf >= 0 else {}),
                 **({"prec_sweeps": ps} if ps >= 0 else {}),
                 **({"prec_interval": (ia.value, ib.value)} if has_iv else {}),

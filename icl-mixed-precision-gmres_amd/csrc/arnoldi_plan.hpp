@@ -145,6 +145,15 @@ struct mpg_arnoldi {
     // _F16 (V holds fp16_rne(2^14 v), ld a multiple of 128 entries) or _F16EMU
     // (the same values as fp32). Other than F32: the plain launch forms only.
     int basis = 0;
+    // the copy of A the polynomial preconditioners' sweeps read instead of the
+    // Arnoldi matrix (mpg_arnoldi_set_prec_copy; neumann.hip): MPG_PREC_VALUES_F32
+    // none, _F16 fp16 bits with row exponents, as a SELL copy (prec_sell) or
+    // in CSR order (prec_vals), _F16EMU the same values as fp32 in CSR order.
+    // The caller's memory: the workspace reads it and frees none of it.
+    int prec_kind = 0;
+    const void* prec_vals = nullptr;
+    const int8_t* prec_rexp = nullptr;
+    const mpg_sell* prec_sell = nullptr;
     // the cycle's tail in one launch (k_update_tail_nc): where it keeps the x
     // it read (mpg_arnoldi_set_x_snapshot), and whether its rotated column
     // H(:, m-1) still waits in tail_stage() for the finish launch

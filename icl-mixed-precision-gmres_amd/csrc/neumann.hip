@@ -40,6 +40,16 @@
 // differ from the lane's own operand p (a pair's second half gathers t), and
 // the second output may be p, never the gathered vector. mpg_gmres_poly_roots
 // gives the roots in the order the product is stable in.
+//
+// The sweeps on an fp16 copy of A (the value type VI = half_v beside the
+// vectors' T = float; mpg_*_sweep_f16f32, mpg_arnoldi_set_prec_copy): the values
+// are mpg_csr_half_values' with scale = 1, row i's entries times 2^e_i, and
+//
+//   s_i = T(ldexp(sum_j half(a_ij) z_in[j], -e_i))
+//
+// summed in the same class and order, the unscale (exact: a power of two)
+// applied once to the finished sum and the epilogues unchanged. Row i's
+// exponent is one more epilogue operand, loaded with the others.
 #include "arnoldi_prologue.hpp"
 #include "mpgmres/solve.h"
 
@@ -73,6 +83,39 @@ template <class T>
 struct ChebArgs {
     const T* z_prev;
     T alpha, beta;
+};
+
+// ... and what a sweep on a scaled fp16 copy takes besides those: the row exponents
+template <class T>
+struct HalfArgs : ChebArgs<T> {
+    const int8_t* rexp;
+};
+template <class T, class VI>
+struct SweepArgs {
+    using type = ChebArgs<T>;
+};
+template <class T>
+struct SweepArgs<T, half_v> {
+    using type = HalfArgs<T>;
+};
+template <class T, class VI>
+__host__ __device__ inline typename SweepArgs<T, VI>::type sweep_args(const ChebArgs<T>& ch, const int8_t* rexp) {
+    if constexpr (std::is_same_v<VI, half_v>) return {ch, rexp};
+    else return ch;
+}
+
+// row i's exponent of a scaled fp16 copy, an epilogue operand like the others;
+// unscale(sum) = sum 2^-e. A value type of the vectors' own carries nothing.
+template <class VI>
+struct RowExp {
+    template <class AR> __device__ __forceinline__ void load(const AR&, int) {}
+    template <class A> __device__ __forceinline__ A unscale(A sum) const { return sum; }
+};
+template <>
+struct RowExp<half_v> {
+    int e;
+    template <class AR> __device__ __forceinline__ void load(const AR& ar, int i) { e = ar.rexp[i]; }
+    template <class A> __device__ __forceinline__ A unscale(A sum) const { return ldexp(sum, -e); }
 };
 
 template <class T, int E>
@@ -153,36 +196,48 @@ __device__ __forceinline__ void sweep_store(int i, T s, const SweepOps<T, E>& o,
 }
 
 // (r and z_out carry no __restrict__: they may be one vector)
-template <class T, class A, int E>
+// VI: the matrix values' type, T or (T = float) half_v with its row exponents in ch
+template <class T, class A, int E, class VI = T>
 __global__ __launch_bounds__(kBlock) void k_csr_sweep(const int32_t* __restrict__ blocks, int nblocks,
                                                       const int32_t* __restrict__ rowptr,
-                                                      const int32_t* __restrict__ col, const T* __restrict__ val,
+                                                      const int32_t* __restrict__ col, const VI* __restrict__ val,
                                                       int64_t nnz, const T* __restrict__ dinv, const T* r,
-                                                      const T* __restrict__ z_in, T* z_out, ChebArgs<T> ch) {
+                                                      const T* __restrict__ z_in, T* z_out,
+                                                      typename SweepArgs<T, VI>::type ch) {
     __shared__ double prod[kNnzCap];
     __shared__ double scratch[kBlock / kWave];
+    struct Pre {
+        SweepOps<T, E> o;
+        RowExp<VI> x;
+    };
     for_rows<false, false, A>(
         blocks, nblocks, rowptr, col, val, nnz, [&](int c) { return (double)z_in[c]; },
-        [&](int i) { return sweep_ops<E>(r, dinv, z_in, ch.z_prev, i); },
-        [&](int i, A sum, const SweepOps<T, E>& o) { sweep_store<E>(i, (T)sum, o, z_out, ch); }, prod, scratch);
+        [&](int i) {
+            Pre p{sweep_ops<E>(r, dinv, z_in, ch.z_prev, i), {}};
+            p.x.load(ch, i);
+            return p;
+        },
+        [&](int i, A sum, const Pre& p) { sweep_store<E>(i, (T)p.x.unscale(sum), p.o, z_out, ch); }, prod, scratch);
 }
 
-template <class T, class CI, int W, bool UNI, class A, int E>
+// (SV: the slices' and the CSR-summed rows' stored values, raw fp16 bits for VI = half_v)
+template <class T, class CI, int W, bool UNI, class A, int E, class VI = T, class SV = typename SellStore<VI>::type>
 __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const int64_t* __restrict__ off,
-                                                       const CI* __restrict__ col, const T* __restrict__ val,
+                                                       const CI* __restrict__ col, const SV* __restrict__ val,
                                                        const int32_t* __restrict__ sbase,
                                                        const int32_t* __restrict__ spat,
                                                        const int64_t* __restrict__ coff, const CI* __restrict__ pat,
                                                        const int32_t* __restrict__ xrp,
-                                                       const int32_t* __restrict__ xcol, const T* __restrict__ xval,
+                                                       const int32_t* __restrict__ xcol, const SV* __restrict__ xval,
                                                        const T* __restrict__ dinv, const T* r,
                                                        const T* __restrict__ z_in, T* z_out, int64_t ustride, int xcd,
-                                                       const int32_t* __restrict__ rows, ChebArgs<T> ch) {
+                                                       const int32_t* __restrict__ rows,
+                                                       typename SweepArgs<T, VI>::type ch) {
     const int lane = threadIdx.x & (kWave - 1), wid = wave_id();
     const int s = (xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x) * (kBlock / kWave) + wid;
     if (s >= nslices) return;  // (no workgroup barrier below)
     const int row0 = s * kWave;
-    SellRow<T, CI, W> row;
+    SellRow<SV, CI, W> row;
     if constexpr (UNI) row.init_uniform(s, ustride, spat, coff);
     else row.init_load(s, off, spat, coff);
     __builtin_amdgcn_sched_barrier(0);
@@ -190,6 +245,8 @@ __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const
     const int i = rows ? rows[row0 + lane] : row0 + lane;
     const int ic = i < n ? i : 0;
     const SweepOps<T, E> o = sweep_ops<E>(r, dinv, z_in, ch.z_prev, ic);
+    RowExp<VI> rx;
+    rx.load(ch, ic);
     __builtin_amdgcn_sched_barrier(0);
     row.init_finish(lane, col, val, sbase, pat);
     row.load(0);
@@ -205,22 +262,23 @@ __global__ __launch_bounds__(kBlock) void k_sell_sweep(int n, int nslices, const
             row.sum(q, xv, sum);
         }
     }
-    if (i < n) sweep_store<E>(i, (T)sum, o, z_out, ch);
+    if (i < n) sweep_store<E>(i, (T)rx.unscale(sum), o, z_out, ch);
 }
 
-template <class T, class A, int E>
-int csr_sweep(mpg_ctx* ctx, const mpg_csr* M, int grid, const T* vals, const T* dinv, const T* r, const T* z_in,
-              T* z_out, ChebArgs<T> ch = {}) {
+template <class T, class A, int E, class VI = T>
+int csr_sweep(mpg_ctx* ctx, const mpg_csr* M, int grid, const VI* vals, const T* dinv, const T* r, const T* z_in,
+              T* z_out, ChebArgs<T> ch = {}, const int8_t* rexp = nullptr) {
     if (M->rows == 0) return MPG_OK;
-    k_csr_sweep<T, A, E><<<grid, kBlock, 0, ctx->stream>>>(M->blocks, M->nblocks, M->rowptr, M->col, vals, M->nnz, dinv,
-                                                           r, z_in, z_out, ch);
+    k_csr_sweep<T, A, E, VI><<<grid, kBlock, 0, ctx->stream>>>(M->blocks, M->nblocks, M->rowptr, M->col, vals, M->nnz,
+                                                               dinv, r, z_in, z_out, sweep_args<T, VI>(ch, rexp));
     MPG_LAUNCH_CHECK(ctx);
     return MPG_OK;
 }
 
-template <class T, class A, int E>
+template <class T, class A, int E, class VI = T>
 int sell_sweep(mpg_ctx* ctx, const SellCopy& S, const T* dinv, const T* r, const T* z_in, T* z_out,
-               ChebArgs<T> ch = {}) {
+               ChebArgs<T> ch = {}, const int8_t* rexp = nullptr) {
+    using SV = typename SellStore<VI>::type;
     if (S.nslices == 0) return MPG_OK;
     const int grid = (S.nslices + kBlock / kWave - 1) / (kBlock / kWave);
     const char* xe = std::getenv("MPG_SELL_XCD");
@@ -230,73 +288,91 @@ int sell_sweep(mpg_ctx* ctx, const SellCopy& S, const T* dinv, const T* r, const
         constexpr int Wc = decltype(wc)::value;
         auto go = [&](auto kern) {
             kern<<<grid, kBlock, 0, ctx->stream>>>(S.n, S.nslices, S.off, static_cast<const CI*>(S.col),
-                                                   static_cast<const T*>(S.val), S.sbase, S.spat, S.coff,
+                                                   static_cast<const SV*>(S.val), S.sbase, S.spat, S.coff,
                                                    static_cast<const CI*>(S.pat), S.xrp, S.xcol,
-                                                   static_cast<const T*>(S.xval), dinv, r, z_in, z_out, S.ustride, xcd,
-                                                   S.rows, ch);
+                                                   static_cast<const SV*>(S.xval), dinv, r, z_in, z_out, S.ustride, xcd,
+                                                   S.rows, sweep_args<T, VI>(ch, rexp));
             return (int)MPG_OK;
         };
-        return sell_uniform(S) ? go(k_sell_sweep<T, CI, Wc, true, A, E>) : go(k_sell_sweep<T, CI, Wc, false, A, E>);
+        return sell_uniform(S) ? go(k_sell_sweep<T, CI, Wc, true, A, E, VI>)
+                               : go(k_sell_sweep<T, CI, Wc, false, A, E, VI>);
     });
     if (st) return st;
     MPG_LAUNCH_CHECK(ctx);
     return MPG_OK;
 }
 
+// The matrix a sweep reads: a SELL copy (S), else CSR row blocks (M, grid,
+// vals). rexp: its values are fp16 bits scaled per row, with these exponents
+// (T = float only); NULL: values of the vectors' type.
+struct SweepMat {
+    const SellCopy* S;
+    const mpg_csr* M;
+    int grid;
+    const void* vals;
+    const int8_t* rexp;
+};
+
+template <class T, class A, int E>
+int sweep(mpg_ctx* ctx, const SweepMat& m, const T* dinv, const T* r, const T* z_in, T* z_out, ChebArgs<T> ch = {}) {
+    if constexpr (std::is_same_v<T, float>) {
+        if (m.rexp)
+            return m.S ? sell_sweep<T, A, E, half_v>(ctx, *m.S, dinv, r, z_in, z_out, ch, m.rexp)
+                       : csr_sweep<T, A, E, half_v>(ctx, m.M, m.grid, static_cast<const half_v*>(m.vals), dinv, r,
+                                                    z_in, z_out, ch, m.rexp);
+    }
+    if (m.rexp) return MPG_ERR_UNSUPPORTED;
+    return m.S ? sell_sweep<T, A, E>(ctx, *m.S, dinv, r, z_in, z_out, ch)
+               : csr_sweep<T, A, E>(ctx, m.M, m.grid, static_cast<const T*>(m.vals), dinv, r, z_in, z_out, ch);
+}
+
 // the Chebyshev step on either storage: the first-step form when there is no z_prev
 template <class T, class A>
-int cheb_sweep(mpg_ctx* ctx, const SellCopy* S, const mpg_csr* M, int grid, const T* vals, const T* dinv, const T* r,
-               const T* z_in, const T* z_prev, T* z_out, T alpha, T beta) {
+int cheb_sweep(mpg_ctx* ctx, const SweepMat& m, const T* dinv, const T* r, const T* z_in, const T* z_prev, T* z_out,
+               T alpha, T beta) {
     const ChebArgs<T> ch{z_prev, alpha, beta};
-    if (S)
-        return z_prev ? sell_sweep<T, A, kCheb>(ctx, *S, dinv, r, z_in, z_out, ch)
-                      : sell_sweep<T, A, kChebFirst>(ctx, *S, dinv, r, z_in, z_out, ch);
-    return z_prev ? csr_sweep<T, A, kCheb>(ctx, M, grid, vals, dinv, r, z_in, z_out, ch)
-                  : csr_sweep<T, A, kChebFirst>(ctx, M, grid, vals, dinv, r, z_in, z_out, ch);
+    return z_prev ? sweep<T, A, kCheb>(ctx, m, dinv, r, z_in, z_out, ch)
+                  : sweep<T, A, kChebFirst>(ctx, m, dinv, r, z_in, z_out, ch);
+}
+
+// The stand-alone entries' matrix (vals: T values, or with row_exp fp16 bits;
+// row_exp of a SELL copy: it must be an MPG_F16 one). false: MPG_ERR_ARG.
+bool api_mat(mpg_ctx* ctx, const mpg_csr* M, const void* vals, const int8_t* row_exp, bool half, SweepMat& m) {
+    if (!ctx || !M || M->rows != M->cols || (M->nnz > 0 && !vals) || (half && !row_exp)) return false;
+    m = SweepMat{nullptr, M, M->nblocks, vals, half ? row_exp : nullptr};
+    return true;
+}
+bool api_mat(mpg_ctx* ctx, const mpg_sell* M, int vtype, const int8_t* row_exp, SweepMat& m) {
+    if (!ctx || !M || M->S.vtype != vtype || M->cols != M->S.n || (vtype == MPG_F16 && !row_exp)) return false;
+    m = SweepMat{&M->S, nullptr, 0, nullptr, vtype == MPG_F16 ? row_exp : nullptr};
+    return true;
+}
+int mat_rows(const SweepMat& m) { return m.S ? m.S->n : m.M->rows; }
+
+template <class T>
+int sweep_api(mpg_ctx* ctx, const SweepMat& m, const T* dinv, const T* r, const T* z_in, T* z_out) {
+    if (mat_rows(m) > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
+    if (mat_rows(m) == 0) return MPG_OK;
+    return sweep<T, double, kNeumann>(ctx, m, dinv, r, z_in, z_out);
 }
 
 template <class T>
-int csr_sweep_api(mpg_ctx* ctx, mpg_csr* M, const T* vals, const T* dinv, const T* r, const T* z_in, T* z_out) {
-    if (!ctx || !M || M->rows != M->cols || (M->nnz > 0 && !vals)) return MPG_ERR_ARG;
-    if (M->rows > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
-    return csr_sweep<T, double, kNeumann>(ctx, M, M->nblocks, vals, dinv, r, z_in, z_out);
-}
-
-template <class T, int VT>
-int sell_sweep_api(mpg_ctx* ctx, mpg_sell* M, const T* dinv, const T* r, const T* z_in, T* z_out) {
-    if (!ctx || !M || M->S.vtype != VT || M->cols != M->S.n) return MPG_ERR_ARG;
-    if (M->S.n > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
-    return sell_sweep<T, double, kNeumann>(ctx, M->S, dinv, r, z_in, z_out);
-}
-
-template <class T>
-int csr_cheb_api(mpg_ctx* ctx, mpg_csr* M, const T* vals, const T* dinv, const T* r, const T* z_in, const T* z_prev,
-                 T* z_out, T alpha, T beta) {
-    if (!ctx || !M || M->rows != M->cols || (M->nnz > 0 && !vals)) return MPG_ERR_ARG;
-    if (M->rows > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
-    if (M->rows == 0) return MPG_OK;
-    return cheb_sweep<T, double>(ctx, nullptr, M, M->nblocks, vals, dinv, r, z_in, z_prev, z_out, alpha, beta);
-}
-
-template <class T, int VT>
-int sell_cheb_api(mpg_ctx* ctx, mpg_sell* M, const T* dinv, const T* r, const T* z_in, const T* z_prev, T* z_out,
-                  T alpha, T beta) {
-    if (!ctx || !M || M->S.vtype != VT || M->cols != M->S.n) return MPG_ERR_ARG;
-    if (M->S.n > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
-    return cheb_sweep<T, double>(ctx, &M->S, nullptr, 0, static_cast<const T*>(nullptr), dinv, r, z_in, z_prev, z_out,
-                                 alpha, beta);
+int cheb_api(mpg_ctx* ctx, const SweepMat& m, const T* dinv, const T* r, const T* z_in, const T* z_prev, T* z_out,
+             T alpha, T beta) {
+    if (mat_rows(m) > 0 && (!dinv || !r || !z_in || !z_out || z_out == z_in)) return MPG_ERR_ARG;
+    if (mat_rows(m) == 0) return MPG_OK;
+    return cheb_sweep<T, double>(ctx, m, dinv, r, z_in, z_prev, z_out, alpha, beta);
 }
 
 // one sweep of the GMRES polynomial on either storage: g gathered, p the
 // lane's own operand, z in place, out the second output (NULL: the last form)
 template <class T, class A>
-int poly_sweep(mpg_ctx* ctx, const SellCopy* S, const mpg_csr* M, int grid, const T* vals, const T* dinv, const T* g,
-               const T* p, T* z, T* out, bool pair, bool first, T c0, T c1) {
+int poly_sweep(mpg_ctx* ctx, const SweepMat& m, const T* dinv, const T* g, const T* p, T* z, T* out, bool pair,
+               bool first, T c0, T c1) {
     const ChebArgs<T> ch{z, c0, c1};
     auto go = [&](auto e) {
         constexpr int E = decltype(e)::value;
-        return S ? sell_sweep<T, A, E>(ctx, *S, dinv, p, g, out, ch)
-                 : csr_sweep<T, A, E>(ctx, M, grid, vals, dinv, p, g, out, ch);
+        return sweep<T, A, E>(ctx, m, dinv, p, g, out, ch);
     };
     if (pair)
         return first ? go(std::integral_constant<int, kPolyPairFirst>{}) : go(std::integral_constant<int, kPolyPair>{});
@@ -313,22 +389,20 @@ bool poly_vectors_ok(const T* dinv, const T* g, const T* p, const T* z, const T*
 }
 
 template <class T>
-int csr_poly_api(mpg_ctx* ctx, mpg_csr* M, const T* vals, const T* dinv, const T* g, const T* p, T* z, T* out, int form,
-                 int first, int last, T c0, T c1) {
-    if (!ctx || !M || M->rows != M->cols || (M->nnz > 0 && !vals)) return MPG_ERR_ARG;
-    if (M->rows > 0 && !poly_vectors_ok(dinv, g, p, z, out, form, last)) return MPG_ERR_ARG;
-    if (M->rows == 0) return MPG_OK;
-    return poly_sweep<T, double>(ctx, nullptr, M, M->nblocks, vals, dinv, g, p, z, out, form == MPG_POLY_PAIR,
-                                 first != 0, c0, c1);
+int poly_api(mpg_ctx* ctx, const SweepMat& m, const T* dinv, const T* g, const T* p, T* z, T* out, int form, int first,
+             int last, T c0, T c1) {
+    if (mat_rows(m) > 0 && !poly_vectors_ok(dinv, g, p, z, out, form, last)) return MPG_ERR_ARG;
+    if (mat_rows(m) == 0) return MPG_OK;
+    return poly_sweep<T, double>(ctx, m, dinv, g, p, z, out, form == MPG_POLY_PAIR, first != 0, c0, c1);
 }
 
-template <class T, int VT>
-int sell_poly_api(mpg_ctx* ctx, mpg_sell* M, const T* dinv, const T* g, const T* p, T* z, T* out, int form, int first,
-                  int last, T c0, T c1) {
-    if (!ctx || !M || M->S.vtype != VT || M->cols != M->S.n) return MPG_ERR_ARG;
-    if (M->S.n > 0 && !poly_vectors_ok(dinv, g, p, z, out, form, last)) return MPG_ERR_ARG;
-    return poly_sweep<T, double>(ctx, &M->S, nullptr, 0, static_cast<const T*>(nullptr), dinv, g, p, z, out,
-                                 form == MPG_POLY_PAIR, first != 0, c0, c1);
+// The matrix a workspace's sweeps read: the copy of mpg_arnoldi_set_prec_copy
+// when one is set, else the Arnoldi matrix in the storage the SpMV runs on
+SweepMat run_mat(const mpg_arnoldi* a) {
+    if (a->prec_kind == MPG_PREC_VALUES_F16)
+        return {a->prec_sell ? &a->prec_sell->S : nullptr, a->d.A, a->Grb, a->prec_vals, a->prec_rexp};
+    if (a->prec_kind == MPG_PREC_VALUES_F16EMU) return {nullptr, a->d.A, a->Grb, a->prec_vals, nullptr};
+    return {a->sell.nslices > 0 ? &a->sell : nullptr, a->d.A, a->Grb, a->d.val_inner, nullptr};
 }
 
 template <class T>
@@ -346,14 +420,11 @@ int neumann_run(mpg_arnoldi* a, int steps, T* w, T* work0, T* work1) {
     const int n = a->d.n;
     if (int st = gdmv_t<T>(ctx, n, T(1), d, w, steps == 1 ? w : work0)) return st;
     T* bufs[2] = {work0, work1};
+    const SweepMat mat = run_mat(a);
     for (int j = 1; j < steps; ++j) {
         const T* z_in = bufs[(j - 1) & 1];
         T* z_out = j == steps - 1 ? w : bufs[j & 1];
-        const int st = a->sell.nslices > 0
-                           ? sell_sweep<T, A, kNeumann>(ctx, a->sell, d, w, z_in, z_out)
-                           : csr_sweep<T, A, kNeumann>(ctx, a->d.A, a->Grb, static_cast<const T*>(a->d.val_inner), d,
-                                                       w, z_in, z_out);
-        if (st) return st;
+        if (int st = sweep<T, A, kNeumann>(ctx, mat, d, w, z_in, z_out)) return st;
     }
     return MPG_OK;
 }
@@ -371,14 +442,12 @@ int cheb_run(mpg_arnoldi* a, int steps, double theta, double delta, T* w, T* wor
     if (int st = mpg_cheb_coeffs(steps, theta, delta, alpha, beta)) return st;
     if (int st = gdmv_t<T>(ctx, n, (T)alpha[0], d, w, steps == 1 ? w : work0)) return st;
     T* bufs[2] = {work0, work1};
-    const SellCopy* S = a->sell.nslices > 0 ? &a->sell : nullptr;
+    const SweepMat mat = run_mat(a);
     for (int j = 1; j < steps; ++j) {
         const T* z_in = bufs[(j - 1) & 1];
         const T* z_prev = j == 1 ? nullptr : bufs[j & 1];
         T* z_out = j == steps - 1 ? w : bufs[j & 1];
-        if (int st = cheb_sweep<T, A>(ctx, S, a->d.A, a->Grb, static_cast<const T*>(a->d.val_inner), d, w, z_in, z_prev,
-                                      z_out, (T)alpha[j], (T)beta[j]))
-            return st;
+        if (int st = cheb_sweep<T, A>(ctx, mat, d, w, z_in, z_prev, z_out, (T)alpha[j], (T)beta[j])) return st;
     }
     return MPG_OK;
 }
@@ -412,10 +481,9 @@ int poly_run(mpg_arnoldi* a, int count, const double* re, const double* im, T* w
     const int n = a->d.n;
     if (count == 1) return gdmv_t<T>(ctx, n, (T)(1.0 / re[0]), d, w, w);
     if (int st = gdmv_t<T>(ctx, n, T(1), d, w, work0)) return st;
-    const SellCopy* S = a->sell.nslices > 0 ? &a->sell : nullptr;
-    const T* vals = static_cast<const T*>(a->d.val_inner);
+    const SweepMat mat = run_mat(a);
     auto sweep = [&](const T* g, const T* p, T* out, bool pair, bool first, double c0, double c1) {
-        return poly_sweep<T, A>(ctx, S, a->d.A, a->Grb, vals, d, g, p, w, out, pair, first, (T)c0, (T)c1);
+        return poly_sweep<T, A>(ctx, mat, d, g, p, w, out, pair, first, (T)c0, (T)c1);
     };
     // the coefficient that adds root k's own term ahead of its sweep (0: a pair adds its own)
     auto omega_at = [&](int k) { return im[k] != 0.0 ? 0.0 : 1.0 / re[k]; };
@@ -648,36 +716,71 @@ extern "C" {
 
 int mpg_csr_jacobi_sweep_f64(mpg_ctx_t c, mpg_csr_t A, const double* vals, const double* dinv, const double* r,
                              const double* z_in, double* z_out) {
-    return csr_sweep_api<double>(c, A, vals, dinv, r, z_in, z_out);
+    SweepMat m;
+    return api_mat(c, A, vals, nullptr, false, m) ? sweep_api<double>(c, m, dinv, r, z_in, z_out) : MPG_ERR_ARG;
 }
 int mpg_csr_jacobi_sweep_f32(mpg_ctx_t c, mpg_csr_t A, const float* vals, const float* dinv, const float* r,
                              const float* z_in, float* z_out) {
-    return csr_sweep_api<float>(c, A, vals, dinv, r, z_in, z_out);
+    SweepMat m;
+    return api_mat(c, A, vals, nullptr, false, m) ? sweep_api<float>(c, m, dinv, r, z_in, z_out) : MPG_ERR_ARG;
+}
+int mpg_csr_jacobi_sweep_f16f32(mpg_ctx_t c, mpg_csr_t A, const uint16_t* vals_half, const int8_t* row_exp,
+                                const float* dinv, const float* r, const float* z_in, float* z_out) {
+    SweepMat m;
+    return api_mat(c, A, vals_half, row_exp, true, m) ? sweep_api<float>(c, m, dinv, r, z_in, z_out) : MPG_ERR_ARG;
 }
 int mpg_sell_jacobi_sweep_f64(mpg_ctx_t c, mpg_sell_t A, const double* dinv, const double* r, const double* z_in,
                               double* z_out) {
-    return sell_sweep_api<double, MPG_F64>(c, A, dinv, r, z_in, z_out);
+    SweepMat m;
+    return api_mat(c, A, MPG_F64, nullptr, m) ? sweep_api<double>(c, m, dinv, r, z_in, z_out) : MPG_ERR_ARG;
 }
 int mpg_sell_jacobi_sweep_f32(mpg_ctx_t c, mpg_sell_t A, const float* dinv, const float* r, const float* z_in,
                               float* z_out) {
-    return sell_sweep_api<float, MPG_F32>(c, A, dinv, r, z_in, z_out);
+    SweepMat m;
+    return api_mat(c, A, MPG_F32, nullptr, m) ? sweep_api<float>(c, m, dinv, r, z_in, z_out) : MPG_ERR_ARG;
+}
+int mpg_sell_jacobi_sweep_f16f32(mpg_ctx_t c, mpg_sell_t A, const int8_t* row_exp, const float* dinv, const float* r,
+                                 const float* z_in, float* z_out) {
+    SweepMat m;
+    return api_mat(c, A, MPG_F16, row_exp, m) ? sweep_api<float>(c, m, dinv, r, z_in, z_out) : MPG_ERR_ARG;
 }
 
 int mpg_csr_cheb_sweep_f64(mpg_ctx_t c, mpg_csr_t A, const double* vals, const double* dinv, const double* r,
                            const double* z_in, const double* z_prev, double* z_out, double alpha, double beta) {
-    return csr_cheb_api<double>(c, A, vals, dinv, r, z_in, z_prev, z_out, alpha, beta);
+    SweepMat m;
+    return api_mat(c, A, vals, nullptr, false, m) ? cheb_api<double>(c, m, dinv, r, z_in, z_prev, z_out, alpha, beta)
+                                                  : MPG_ERR_ARG;
 }
 int mpg_csr_cheb_sweep_f32(mpg_ctx_t c, mpg_csr_t A, const float* vals, const float* dinv, const float* r,
                            const float* z_in, const float* z_prev, float* z_out, float alpha, float beta) {
-    return csr_cheb_api<float>(c, A, vals, dinv, r, z_in, z_prev, z_out, alpha, beta);
+    SweepMat m;
+    return api_mat(c, A, vals, nullptr, false, m) ? cheb_api<float>(c, m, dinv, r, z_in, z_prev, z_out, alpha, beta)
+                                                  : MPG_ERR_ARG;
+}
+int mpg_csr_cheb_sweep_f16f32(mpg_ctx_t c, mpg_csr_t A, const uint16_t* vals_half, const int8_t* row_exp,
+                              const float* dinv, const float* r, const float* z_in, const float* z_prev, float* z_out,
+                              float alpha, float beta) {
+    SweepMat m;
+    return api_mat(c, A, vals_half, row_exp, true, m) ? cheb_api<float>(c, m, dinv, r, z_in, z_prev, z_out, alpha, beta)
+                                                      : MPG_ERR_ARG;
 }
 int mpg_sell_cheb_sweep_f64(mpg_ctx_t c, mpg_sell_t A, const double* dinv, const double* r, const double* z_in,
                             const double* z_prev, double* z_out, double alpha, double beta) {
-    return sell_cheb_api<double, MPG_F64>(c, A, dinv, r, z_in, z_prev, z_out, alpha, beta);
+    SweepMat m;
+    return api_mat(c, A, MPG_F64, nullptr, m) ? cheb_api<double>(c, m, dinv, r, z_in, z_prev, z_out, alpha, beta)
+                                              : MPG_ERR_ARG;
 }
 int mpg_sell_cheb_sweep_f32(mpg_ctx_t c, mpg_sell_t A, const float* dinv, const float* r, const float* z_in,
                             const float* z_prev, float* z_out, float alpha, float beta) {
-    return sell_cheb_api<float, MPG_F32>(c, A, dinv, r, z_in, z_prev, z_out, alpha, beta);
+    SweepMat m;
+    return api_mat(c, A, MPG_F32, nullptr, m) ? cheb_api<float>(c, m, dinv, r, z_in, z_prev, z_out, alpha, beta)
+                                              : MPG_ERR_ARG;
+}
+int mpg_sell_cheb_sweep_f16f32(mpg_ctx_t c, mpg_sell_t A, const int8_t* row_exp, const float* dinv, const float* r,
+                               const float* z_in, const float* z_prev, float* z_out, float alpha, float beta) {
+    SweepMat m;
+    return api_mat(c, A, MPG_F16, row_exp, m) ? cheb_api<float>(c, m, dinv, r, z_in, z_prev, z_out, alpha, beta)
+                                              : MPG_ERR_ARG;
 }
 
 int mpg_csr_jacobi_bound_f64(mpg_ctx_t c, mpg_csr_t A, const double* vals, const double* dinv, double* b_host) {
@@ -712,21 +815,67 @@ int mpg_cheb_coeffs(int steps, double theta, double delta, double* alpha, double
 int mpg_csr_poly_sweep_f64(mpg_ctx_t c, mpg_csr_t A, const double* vals, const double* dinv, const double* g,
                            const double* p, double* z, double* out, int32_t form, int32_t first, int32_t last,
                            double c0, double c1) {
-    return csr_poly_api<double>(c, A, vals, dinv, g, p, z, out, form, first, last, c0, c1);
+    SweepMat m;
+    return api_mat(c, A, vals, nullptr, false, m) ? poly_api<double>(c, m, dinv, g, p, z, out, form, first, last, c0, c1)
+                                                  : MPG_ERR_ARG;
 }
 int mpg_csr_poly_sweep_f32(mpg_ctx_t c, mpg_csr_t A, const float* vals, const float* dinv, const float* g,
                            const float* p, float* z, float* out, int32_t form, int32_t first, int32_t last, float c0,
                            float c1) {
-    return csr_poly_api<float>(c, A, vals, dinv, g, p, z, out, form, first, last, c0, c1);
+    SweepMat m;
+    return api_mat(c, A, vals, nullptr, false, m) ? poly_api<float>(c, m, dinv, g, p, z, out, form, first, last, c0, c1)
+                                                  : MPG_ERR_ARG;
+}
+int mpg_csr_poly_sweep_f16f32(mpg_ctx_t c, mpg_csr_t A, const uint16_t* vals_half, const int8_t* row_exp,
+                              const float* dinv, const float* g, const float* p, float* z, float* out, int32_t form,
+                              int32_t first, int32_t last, float c0, float c1) {
+    SweepMat m;
+    return api_mat(c, A, vals_half, row_exp, true, m)
+               ? poly_api<float>(c, m, dinv, g, p, z, out, form, first, last, c0, c1)
+               : MPG_ERR_ARG;
 }
 int mpg_sell_poly_sweep_f64(mpg_ctx_t c, mpg_sell_t A, const double* dinv, const double* g, const double* p, double* z,
                             double* out, int32_t form, int32_t first, int32_t last, double c0, double c1) {
-    return sell_poly_api<double, MPG_F64>(c, A, dinv, g, p, z, out, form, first, last, c0, c1);
+    SweepMat m;
+    return api_mat(c, A, MPG_F64, nullptr, m) ? poly_api<double>(c, m, dinv, g, p, z, out, form, first, last, c0, c1)
+                                              : MPG_ERR_ARG;
 }
 int mpg_sell_poly_sweep_f32(mpg_ctx_t c, mpg_sell_t A, const float* dinv, const float* g, const float* p, float* z,
                             float* out, int32_t form, int32_t first, int32_t last, float c0, float c1) {
-    return sell_poly_api<float, MPG_F32>(c, A, dinv, g, p, z, out, form, first, last, c0, c1);
+    SweepMat m;
+    return api_mat(c, A, MPG_F32, nullptr, m) ? poly_api<float>(c, m, dinv, g, p, z, out, form, first, last, c0, c1)
+                                              : MPG_ERR_ARG;
 }
+int mpg_sell_poly_sweep_f16f32(mpg_ctx_t c, mpg_sell_t A, const int8_t* row_exp, const float* dinv, const float* g,
+                               const float* p, float* z, float* out, int32_t form, int32_t first, int32_t last,
+                               float c0, float c1) {
+    SweepMat m;
+    return api_mat(c, A, MPG_F16, row_exp, m) ? poly_api<float>(c, m, dinv, g, p, z, out, form, first, last, c0, c1)
+                                              : MPG_ERR_ARG;
+}
+
+int mpg_arnoldi_set_prec_copy(mpg_arnoldi_t a, int32_t kind, const void* vals, const int8_t* row_exp, mpg_sell_t sell) {
+    if (!a || kind < MPG_PREC_VALUES_F32 || kind > MPG_PREC_VALUES_F16EMU) return MPG_ERR_ARG;
+    if (kind == MPG_PREC_VALUES_F32) {
+        if (vals || row_exp || sell) return MPG_ERR_ARG;
+    } else {
+        // an fp32 Arnoldi on fp32 values of one GPU's rows (mpg_arnoldi_neumann_apply's combinations, less fp64)
+        if ((a->combo != 2 && a->combo != 3) || a->d.inner_val != MPG_F32 || a->front != 0 || a->d.n_ext != a->d.n)
+            return MPG_ERR_UNSUPPORTED;
+        if (kind == MPG_PREC_VALUES_F16EMU ? (sell || row_exp || (a->d.A->nnz > 0 && !vals))
+                                           : (!row_exp || (sell ? vals != nullptr : a->d.A->nnz > 0 && !vals)))
+            return MPG_ERR_ARG;
+        if (sell && (sell->S.vtype != MPG_F16 || sell->S.n != a->d.n || sell->cols != a->d.n || sell->S.nslices == 0))
+            return MPG_ERR_ARG;
+    }
+    a->prec_kind = kind;
+    a->prec_vals = vals;
+    a->prec_rexp = row_exp;
+    a->prec_sell = sell;
+    return MPG_OK;
+}
+
+int mpg_arnoldi_prec_values(mpg_arnoldi_t a) { return a ? a->prec_kind : MPG_ERR_ARG; }
 
 // (host arithmetic, here for mpg_cheb_coeffs' reason)
 int mpg_gmres_poly_roots(int s, const double* H, int ldh, double* re, double* im, int* count) {

@@ -146,6 +146,27 @@ __global__ __launch_bounds__(kBlock) void k_half_rows(int32_t rows, const int32_
         if (cnt[q]) atomicAdd(stats + q, cnt[q]);
 }
 
+// The scaled fp16 values back as fp32, one thread per row: float(half) 2^-e,
+// exact unless it leaves fp32's range (counted when it overflows).
+// mpg_csr_half_dequant_f32, capi.h.
+__global__ __launch_bounds__(kBlock) void k_half_dequant(int32_t rows, const int32_t* __restrict__ rowptr,
+                                                         const uint16_t* __restrict__ val,
+                                                         const int8_t* __restrict__ rexp, float* __restrict__ out,
+                                                         unsigned long long* __restrict__ bad) {
+    unsigned long long cnt = 0;
+    const int stride = gridDim.x * kBlock;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < rows; i += stride) {
+        const int e = rexp[i];
+        for (int j = rowptr[i], j1 = rowptr[i + 1]; j < j1; ++j) {
+            const float h = to_float(val[j]);
+            const float f = ldexpf(h, -e);
+            cnt += fabsf(h) <= FLT_MAX && !(fabsf(f) <= FLT_MAX);
+            if (out) out[j] = f;
+        }
+    }
+    if (cnt) atomicAdd(bad, cnt);
+}
+
 // ---------------- Jacobi setup (types.hpp:393-431) ----------------
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_rowabs_max(int32_t rows, const int32_t* __restrict__ rowptr,
@@ -316,6 +337,23 @@ int mpg_csr_half_values(mpg_ctx_t c, mpg_csr_t A, const double* vals, int32_t sc
                         (scale ? "" : " (row scaling off)");
         return MPG_ERR_RANGE;
     }
+    return MPG_OK;
+}
+
+int mpg_csr_half_dequant_f32(mpg_ctx_t c, mpg_csr_t A, const uint16_t* vals, const int8_t* row_exp, float* out,
+                             int64_t* nonfinite) {
+    if (!c || !A || !nonfinite || (A->nnz > 0 && !vals) || (A->rows > 0 && !row_exp)) return MPG_ERR_ARG;
+    *nonfinite = 0;
+    if (A->rows == 0) return MPG_OK;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->red_ws);
+    unsigned long long h = 0;
+    if (hipMemsetAsync(d, 0, sizeof h, c->stream) != hipSuccess) return MPG_ERR_HIP;
+    k_half_dequant<<<grid_for(A->rows, 1), kBlock, 0, c->stream>>>(A->rows, A->rowptr, vals, row_exp, out, d);
+    MPG_LAUNCH_CHECK(c);
+    if (hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return MPG_ERR_HIP;
+    *nonfinite = (int64_t)h;
     return MPG_OK;
 }
 

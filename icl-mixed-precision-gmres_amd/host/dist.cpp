@@ -673,6 +673,7 @@ int solve_rank_threads(const mpg_solve_args* a, int32_t P, mpg_solve_result* r, 
 int refuse_basis(const mpg_solve_args* a, mpg_solve_result* r) {
     try {
         check_basis_args(*a, basis_setting(), false, true);
+        check_prec_values_args(*a, prec_values_setting(), false, true);  // (MPG_PREC_VALUES likewise)
     } catch (const StatusError& e) {
         std::snprintf(r->message, sizeof r->message, "%s", e.what());
         return e.status;

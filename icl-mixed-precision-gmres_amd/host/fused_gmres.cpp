@@ -130,6 +130,39 @@ void check_basis_args(const mpg_solve_args& a, int basis, bool surface, bool ran
         refuse("is built for the CSR row-block SpMV only (it exists for the tests): not SELL storage");
 }
 
+int prec_values_setting() {
+    const char* e = std::getenv("MPG_PREC_VALUES");
+    if (!e || !*e) return MPG_PREC_VALUES_F32;
+    const std::string v = e;
+    if (v == "f32") return MPG_PREC_VALUES_F32;
+    if (v == "f16") return MPG_PREC_VALUES_F16;
+    if (v == "f16emu") return MPG_PREC_VALUES_F16EMU;
+    throw StatusError(MPG_ERR_ARG, "MPG_PREC_VALUES = " + v + " is not f32, f16 or f16emu");
+}
+
+const char* prec_values_name(int kind) {
+    return kind == MPG_PREC_VALUES_F16 ? "f16" : kind == MPG_PREC_VALUES_F16EMU ? "f16emu" : "f32";
+}
+
+void check_prec_values_args(const mpg_solve_args& a, int kind, bool surface, bool ranks) {
+    if (kind == MPG_PREC_VALUES_F32) return;
+    const std::string name = std::string("prec_values ") + prec_values_name(kind);
+    auto refuse = [&](const std::string& why) { throw StatusError(MPG_ERR_UNSUPPORTED, name + " " + why); };
+    if (surface)
+        refuse("is not available on the operator-surface engine: the sweeps on an fp16 copy of A are the fused "
+               "engine's");
+    if (ranks) refuse("is not available on a row-partitioned solve: the polynomial preconditioners are not either");
+    const bool sweeps = (a.prec == MPG_PREC_NEUMANN && a.jacobi_steps > 1) || a.prec == MPG_PREC_CHEBYSHEV ||
+                        a.prec == MPG_PREC_GMRES_POLY;
+    if (!sweeps)
+        refuse("needs a preconditioner that sweeps over A (prec neumann with two steps or more, chebyshev, "
+               "gmres_poly): this one reads no copy of A's values in the sweeps' slot");
+    if (a.mode != MPG_MODE_MIXED)
+        refuse("runs in mode mixed only (fp32 sweeps beside an fp32 Arnoldi matrix and an fp64 residual)");
+    if (kind == MPG_PREC_VALUES_F16EMU && a.spmv_format != 0 && a.spmv_format != 1)
+        refuse("is built for the CSR row-block storage only (it exists for the tests): not SELL or node-block storage");
+}
+
 struct FusedEngine::Impl {
     mpg_ctx_t ctx = nullptr;
     mpg_solve_args args{};
@@ -204,6 +237,13 @@ struct FusedEngine::Impl {
     PolyRoots poly_roots{};
     bool jacobi_inside() const { return args.prec == MPG_PREC_JACOBI || (nm_asked == 1 && !cheb && !poly); }
     int basis = MPG_BASIS_F32;  // the basis' storage (MPG_BASIS, read at create; mpg_arnoldi_set_basis)
+    // The copy of A the sweeps read (MPG_PREC_VALUES, read at create;
+    // mpg_arnoldi_set_prec_copy). f16: the row exponents and, where the Arnoldi
+    // runs on a SELL copy, an MPG_F16 SELL copy, else the fp16 bits in CSR
+    // order. f16emu: the dequantised fp32 values in CSR order. f32: nothing.
+    int prec_values = MPG_PREC_VALUES_F32;
+    DevMem pv_vals, pv_exp;
+    mpg_sell_t pv_sell = nullptr;
     // the initial-guess store (FusedEngine::guess_*): g_L columns of capacity,
     // g_p held, panels of leading dimension g_ld (padded to 256 B like the
     // basis); nothing is allocated while g_L == 0
@@ -217,6 +257,7 @@ struct FusedEngine::Impl {
     ~Impl() {
         if (ilu) mpg_ilu_destroy(ilu);
         if (arn) mpg_arnoldi_destroy(arn);
+        if (pv_sell) mpg_sell_destroy(pv_sell);
         if (csr) mpg_csr_destroy(csr);
         for (double* r : rep)
             if (r) (void)hipHostFree(r);
@@ -418,6 +459,8 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     I.nnz = a.nnz;
     I.basis = basis_setting();
     check_basis_args(a, I.basis, false, comm != nullptr);
+    I.prec_values = prec_values_setting();
+    check_prec_values_args(a, I.prec_values, false, comm != nullptr);
     const bool ilu = a.prec == MPG_PREC_ILU || a.prec == MPG_PREC_ILU_JACOBI;
     if (ilu && comm)
         throw std::invalid_argument("ILU / ILU-Jacobi factor the whole matrix: not available on a row-partitioned solve");
@@ -501,6 +544,7 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     // a compressed basis: auto picks among CSR row blocks and the SELL copy
     // (no node blocks); the emulated one is built for the CSR kernel
     if (I.basis != MPG_BASIS_F32 && a.spmv_format == 0) d.spmv_format = I.basis == MPG_BASIS_F16EMU ? 1 : 4;
+    if (I.prec_values == MPG_PREC_VALUES_F16EMU) d.spmv_format = 1;  // (auto or csr: check_prec_values_args)
     d.n_front = n_front;
     {
         const char* benv = std::getenv("MPG_BJACOBI_FUSE");
@@ -518,6 +562,24 @@ FusedEngine::FusedEngine(mpg_ctx_t ctx, const mpg_solve_args& a, Comm* comm, int
     // fp32 Arnoldi: the reference's fp32 accumulation class on request (arnoldi.h)
     if (a.accum) check(mpg_arnoldi_set_accum(I.arn, MPG_ACCUM_F32), "mpg_arnoldi_set_accum", ctx);
     if (I.basis != MPG_BASIS_F32) check(mpg_arnoldi_set_basis(I.arn, I.basis), "mpg_arnoldi_set_basis", ctx);
+    if (I.prec_values == MPG_PREC_VALUES_F16) {
+        // the storage form of the Arnoldi SpMV decides the sweeps': a SELL copy
+        // of the fp16 bits beside a SELL Arnoldi matrix (load_values left the
+        // bits in pv_vals for it; the copy owns its own), else the bits in CSR order
+        int32_t fmt = 0;
+        check(mpg_arnoldi_spmv_layout(I.arn, &fmt, nullptr, nullptr, nullptr, nullptr), "layout", ctx);
+        if (fmt == 2) {
+            check(mpg_sell_create(ctx, I.csr, MPG_F16, I.pv_vals.p, 2, &I.pv_sell), "fp16 SELL copy for the sweeps", ctx);
+            check(mpg_ctx_sync(ctx), "sync", ctx);
+            I.pv_vals = DevMem();
+        }
+        check(mpg_arnoldi_set_prec_copy(I.arn, I.prec_values, I.pv_sell ? nullptr : I.pv_vals.p, I.pv_exp.as<int8_t>(),
+                                        I.pv_sell),
+              "mpg_arnoldi_set_prec_copy", ctx);
+    } else if (I.prec_values == MPG_PREC_VALUES_F16EMU) {
+        check(mpg_arnoldi_set_prec_copy(I.arn, I.prec_values, I.pv_vals.p, nullptr, nullptr),
+              "mpg_arnoldi_set_prec_copy", ctx);
+    }
     // (the GMRES polynomial: for the asked degree, so that the root count of refreshed values fits)
     const int nm_cap = I.poly ? a.jacobi_steps : I.nm_steps;
     if (nm_cap >= 2) I.nm_work0 = DevMem(ctx, (size_t)I.n * dsize(ty.T) + 64);
@@ -614,6 +676,35 @@ void FusedEngine::load_values(const double* val, bool on_device) {
                                   "that needed none, with the unscaled kernels; the engine keeps its matrix -- create "
                                   "a new engine for these values");
     }
+    // The sweeps' fp16 copy (prec_values): converted into scratch first too,
+    // and refused with the old matrix untouched when an entry does not fit --
+    // fp16 after the row scaling, the int8 exponent, or fp32 once unscaled
+    DevMem pv_half, pv_exp_new;
+    if (I.prec_values != MPG_PREC_VALUES_F32) {
+        if (!on_device) {
+            staged = DevMem(ctx, nz1 * 8);
+            if (nz) check(mpg_memcpy_h2d(ctx, staged.p, val, nz * 8), "h2d", ctx);
+            val = staged.as<double>();
+            on_device = true;
+        }
+        pv_half = DevMem(ctx, nz1 * 2);
+        pv_exp_new = DevMem(ctx, (size_t)I.n + 64);
+        int64_t st4[4] = {0, 0, 0, 0}, bad = 0;
+        const std::string name = std::string("prec_values ") + prec_values_name(I.prec_values);
+        const int st = mpg_csr_half_values(ctx, I.csr, val, 1, pv_half.as<uint16_t>(), pv_exp_new.as<int8_t>(), st4);
+        if (st == MPG_ERR_RANGE)
+            throw StatusError(MPG_ERR_RANGE, name + ": the values do not fit the sweeps' fp16 copy (" +
+                                                 std::to_string(st4[2]) + " entries overflow, " +
+                                                 std::to_string(st4[3]) + " row exponents outside int8)" +
+                                                 (live ? "; the engine keeps its matrix" : ""));
+        check(st, "fp16 values for the sweeps", ctx);
+        check(mpg_csr_half_dequant_f32(ctx, I.csr, pv_half.as<uint16_t>(), pv_exp_new.as<int8_t>(), nullptr, &bad),
+              "fp16 values for the sweeps", ctx);
+        if (bad)
+            throw StatusError(MPG_ERR_RANGE, name + ": " + std::to_string(bad) +
+                                                 " entries of the sweeps' fp16 copy overflow fp32 once unscaled" +
+                                                 (live ? "; the engine keeps its matrix" : ""));
+    }
     values_dirty_ = live;  // from here on a failure leaves a live engine without a consistent matrix
 
     // values: the original fp64 A, the residual matrix (outer type) and the
@@ -663,6 +754,24 @@ void FusedEngine::load_values(const double* val, bool on_device) {
                          "(rows spanning more than fp16's range; %lld rows scaled)\n",
                          (long long)I.half_stats[1], (long long)I.half_stats[0]);
         I.val_inner = I.val_inner_own.p;
+    }
+
+    // the sweeps' copy, in place on a live engine: the exponents; the bits in
+    // CSR order (f16 without a SELL copy, which is refilled from the scratch
+    // below) or the dequantised values (f16emu)
+    if (I.prec_values != MPG_PREC_VALUES_F32) {
+        need(I.pv_exp, (size_t)I.n + 64);
+        if (I.n) check(mpg_memcpy_d2d(ctx, I.pv_exp.p, pv_exp_new.p, (size_t)I.n), "d2d", ctx);
+        if (I.prec_values == MPG_PREC_VALUES_F16EMU) {
+            int64_t bad = 0;
+            need(I.pv_vals, nz1 * 4);
+            check(mpg_csr_half_dequant_f32(ctx, I.csr, pv_half.as<uint16_t>(), I.pv_exp.as<int8_t>(),
+                                           I.pv_vals.as<float>(), &bad),
+                  "fp16 values for the sweeps", ctx);
+        } else if (!I.pv_sell) {
+            need(I.pv_vals, nz1 * 2);
+            if (nz) check(mpg_memcpy_d2d(ctx, I.pv_vals.p, pv_half.p, nz * 2), "d2d", ctx);
+        }
     }
 
     // Jacobi<P>(A): fp64 original A for P = double (baseline), else the A
@@ -761,6 +870,8 @@ void FusedEngine::load_values(const double* val, bool on_device) {
     // the workspace's storage copies, from the arrays rewritten above (the
     // descriptor's pointers are unchanged)
     check(mpg_arnoldi_refresh_values(I.arn), "mpg_arnoldi_refresh_values", ctx);
+    if (I.pv_sell)
+        check(mpg_sell_refresh_values(ctx, I.pv_sell, I.csr, MPG_F16, pv_half.p), "fp16 SELL copy for the sweeps", ctx);
     // The captured cycle holds its launch arguments by value. Identity,
     // Jacobi, block Jacobi and the Jacobi sweeps pass addresses only, which
     // did not move: the graph stays. Chebyshev's theta / delta and the
@@ -1498,7 +1609,10 @@ double FusedEngine::phase_bytes(int which) const {
     // written (six n-vectors), less z's read in the first sweep and the second
     // output in the last: with k roots (k - 1) * 6 - 2 n-vectors beside the
     // matrix, k >= 2
-    const double nm = I.nm_steps ? (2 * sT + sP) * n + (I.nm_steps - 1) * (z * (sV + 4) + (n + 1) * 4 + 5 * n * sT) +
+    // (prec_values f16: 2 bytes per value and the n row exponents in each sweep)
+    const double sW = I.prec_values == MPG_PREC_VALUES_F16 ? 2.0 : sV;
+    const double ex = I.prec_values == MPG_PREC_VALUES_F16 ? n : 0.0;
+    const double nm = I.nm_steps ? (2 * sT + sP) * n + (I.nm_steps - 1) * (z * (sW + 4) + ex + (n + 1) * 4 + 5 * n * sT) +
                                        (I.cheb && I.nm_steps > 2 ? (I.nm_steps - 2) * n * sT : 0.0) +
                                        (I.poly && I.nm_steps > 2 ? (I.nm_steps - 3) * n * sT : 0.0) -
                                        (I.poly && I.nm_steps == 2 ? n * sT : 0.0)
@@ -1545,6 +1659,7 @@ double FusedEngine::phase_bytes(int which) const {
 
 mpg_arnoldi_t FusedEngine::arnoldi() const { return p_->arn; }
 int FusedEngine::basis() const { return p_->basis; }
+int FusedEngine::prec_values() const { return p_->prec_values; }
 const int64_t* FusedEngine::half_stats() const { return p_->half_stats; }
 int FusedEngine::prec_fused() const { return p_->bj_bs ? (p_->bj_fused_step ? 1 : 0) : -1; }
 int FusedEngine::prec_sweeps() const { return p_->nm_asked ? p_->nm_asked : -1; }
@@ -1779,6 +1894,10 @@ int mpg_engine_accum(mpg_engine_t e) {
 int mpg_engine_basis(mpg_engine_t e) {
     if (!e || !e->eng) return MPG_ERR_ARG;
     return mpg_arnoldi_basis(e->eng->arnoldi());
+}
+int mpg_engine_prec_values(mpg_engine_t e) {
+    if (!e || !e->eng) return MPG_ERR_ARG;
+    return mpg_arnoldi_prec_values(e->eng->arnoldi());
 }
 
 int mpg_engine_prologue_format(mpg_engine_t e) {

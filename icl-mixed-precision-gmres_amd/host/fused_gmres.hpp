@@ -64,6 +64,17 @@ const char* basis_name(int basis);
 // row-partitioned solve.
 void check_basis_args(const mpg_solve_args& a, int basis, bool surface, bool ranks);
 
+// The matrix values the polynomial preconditioners' sweeps read
+// (mpg_arnoldi_set_prec_copy), from the setting MPG_PREC_VALUES = f32 (default)
+// / f16 / f16emu, read once when an engine is created; any other value is
+// MPG_ERR_ARG naming it.
+int prec_values_setting();
+const char* prec_values_name(int kind);
+// An fp16 or emulated copy runs on the fused engine on one GPU, mode mixed,
+// under prec neumann (two sweeps or more), chebyshev and gmres_poly (f16emu:
+// CSR row blocks): anything else is MPG_ERR_UNSUPPORTED naming the reason.
+void check_prec_values_args(const mpg_solve_args& a, int kind, bool surface, bool ranks);
+
 // Communication seam of the row-partitioned solve: a single-GPU engine has
 // no communicator; a multi-GPU rank supplies one (see comm.hpp).
 class Comm {
@@ -201,6 +212,7 @@ public:
     double phase_bytes(int which) const;
     mpg_arnoldi_t arnoldi() const;
     int basis() const;  // mpg_engine_basis
+    int prec_values() const;  // mpg_engine_prec_values
     // mixed-half: what the fp16 cast of the Arnoldi values did (stats of
     // mpg_csr_half_values, capi.h; zeros in other modes)
     const int64_t* half_stats() const;

@@ -24,6 +24,11 @@
 // bytes per entry, fp16 of 2^14 v, all arithmetic in the Arnoldi precision:
 // mode mixed, cgs / cgsr, rlen <= 32, one GPU; f16emu the same values as fp32;
 // sets MPG_BASIS for this process, mpg_engine_basis in solve.h),
+// --prec-values {f32,f16,f16emu} (the sweeps of --prec neumann / chebyshev /
+// gmres_poly read an fp16 copy of A, 2 bytes per value and an int8 exponent per
+// row; the Arnoldi SpMV and the residual keep theirs; mode mixed, one GPU;
+// f16emu the same values as fp32 on CSR storage; sets MPG_PREC_VALUES for this
+// process, mpg_engine_prec_values in solve.h),
 // --device D, --stop-on-breakdown (end the solve with an error at the first
 // non-finite Arnoldi residual; without it the count goes to stderr),
 // --ngpus N (row-partition the fused solve over N GPUs of this process, one
@@ -114,6 +119,7 @@ int main(int argc, char* argv[]) {
         else if (f == "--cheb-ratio") setenv("MPG_CHEB_RATIO", next(), 1);
         else if (f == "--cheb-lmax") setenv("MPG_CHEB_LMAX", next(), 1);
         else if (f == "--basis") setenv("MPG_BASIS", next(), 1);
+        else if (f == "--prec-values") setenv("MPG_PREC_VALUES", next(), 1);
         else if (f == "--gpu") { /* always on the GPU */ }
         else if (f == "--device") a.device = std::stoi(next());
         else if (f == "--ngpus") ngpus = std::stoi(next());

@@ -211,6 +211,7 @@ void dispatch_mode(const mpg_solve_args& a, const SparseMatrix<double, Hip>& A, 
 
 int solve_surface(const mpg_solve_args& a, mpg_solve_result* r) {
     check_basis_args(a, basis_setting(), true, false);  // (MPG_BASIS: the fused engine's)
+    check_prec_values_args(a, prec_values_setting(), true, false);  // (MPG_PREC_VALUES: likewise)
     if (a.prec == MPG_PREC_NEUMANN) check_neumann_args(a);
     if (a.prec == MPG_PREC_CHEBYSHEV) check_cheb_args(a);
     if (a.prec == MPG_PREC_GMRES_POLY) check_gmres_poly_args(a);

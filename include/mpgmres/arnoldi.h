@@ -149,6 +149,36 @@ int mpg_arnoldi_cheb_apply(mpg_arnoldi_t a, int32_t steps, double theta, double 
  * mpg_arnoldi_neumann_apply; MPG_ERR_ARG also for a root list not as above. */
 int mpg_arnoldi_poly_apply(mpg_arnoldi_t a, int32_t count, const double* re, const double* im, void* w, void* work0,
                            void* work1);
+/* The copy of A that the sweeps of the three applications above read in place
+ * of the workspace's Arnoldi matrix (an addition to the reference's set; the
+ * idea of its single-prec mode, an exact solver around a cheaper
+ * preconditioner, one level down). z_1, the epilogues, the work vectors and
+ * the launch counts do not change; D, the interval and the roots are the
+ * caller's as before.
+ *   MPG_PREC_VALUES_F32     none (default; vals, row_exp and sell NULL).
+ *   MPG_PREC_VALUES_F16     A^ = mpg_csr_half_values(A, scale = 1): fp16 bits
+ *                           and the int8 exponents row_exp (n of them). With
+ *                           sell: an MPG_F16 mpg_sell_t of those bits (vals
+ *                           NULL), swept by mpg_sell_*_sweep_f16f32's kernels;
+ *                           without: vals = the bits in CSR order, swept by
+ *                           mpg_csr_*_sweep_f16f32's. The row sum is
+ *                           T(ldexp(sum_j half(a_ij) z_j, -e_i)) in the
+ *                           workspace's accumulation class, CSR order.
+ *   MPG_PREC_VALUES_F16EMU  the same matrix as fp32 values float(half) 2^-e_i
+ *                           in CSR order (vals; row_exp and sell NULL), swept by
+ *                           mpg_csr_*_sweep_f32's kernel: bit for bit what
+ *                           _F16 computes while no value is an fp32 subnormal
+ *                           (tests).
+ * The arrays and the copy stay the caller's and must outlive their use; a
+ * refill in place needs no new call. MPG_ERR_UNSUPPORTED unless the workspace
+ * is an fp32 Arnoldi on fp32 values without halo rows; MPG_ERR_ARG for another
+ * kind, a missing or surplus argument, or a SELL copy of another value type or
+ * size. mpg_arnoldi_prec_values: the kind set. */
+#define MPG_PREC_VALUES_F32 0
+#define MPG_PREC_VALUES_F16 1
+#define MPG_PREC_VALUES_F16EMU 2
+int mpg_arnoldi_set_prec_copy(mpg_arnoldi_t a, int32_t kind, const void* vals, const int8_t* row_exp, mpg_sell_t sell);
+int mpg_arnoldi_prec_values(mpg_arnoldi_t a);
 
 /* Storage the Arnoldi SpMV runs on: *format 1 = CSR row blocks (cuSPARSE
  * csrmv's input, types_cuda.hpp:53-60), 2 = SELL-64 copy made at create

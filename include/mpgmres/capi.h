@@ -547,6 +547,40 @@ int mpg_sell_poly_sweep_f64(mpg_ctx_t ctx, mpg_sell_t A, const double* dinv, con
 int mpg_sell_poly_sweep_f32(mpg_ctx_t ctx, mpg_sell_t A, const float* dinv, const float* g, const float* p, float* z,
                             float* out, int32_t form, int32_t first, int32_t last, float c0, float c1);
 
+/* ---- the three sweeps on an fp16 copy of A (neumann.hip; an addition to the
+ * reference's set): forms of mpg_{csr,sell}_{jacobi,cheb,poly}_sweep_f32 above
+ * with the matrix values of mpg_csr_half_values(A, scale = 1): fp16 bits
+ * (vals_half in CSR order, or an MPG_F16 mpg_sell_t built from them) and the
+ * int8 row exponents row_exp. Vectors and coefficients are fp32; the row sum is
+ *   s_i = float(ldexp(sum_j half(a_ij) z[j], -row_exp[i]))
+ * (fp64 sums, CSR order; the unscale is exact) and everything after it is the
+ * fp32 entry's. Bit for bit the fp32 entry on the values float(half) 2^-e_i
+ * (mpg_csr_half_dequant_f32) while none of those is an fp32 subnormal.
+ * MPG_ERR_ARG as for the fp32 entries, and for a NULL row_exp or a SELL copy
+ * that is not MPG_F16. One launch each. */
+int mpg_csr_jacobi_sweep_f16f32(mpg_ctx_t ctx, mpg_csr_t A, const uint16_t* vals_half, const int8_t* row_exp,
+                                const float* dinv, const float* r, const float* z_in, float* z_out);
+int mpg_sell_jacobi_sweep_f16f32(mpg_ctx_t ctx, mpg_sell_t A, const int8_t* row_exp, const float* dinv, const float* r,
+                                 const float* z_in, float* z_out);
+int mpg_csr_cheb_sweep_f16f32(mpg_ctx_t ctx, mpg_csr_t A, const uint16_t* vals_half, const int8_t* row_exp,
+                              const float* dinv, const float* r, const float* z_in, const float* z_prev, float* z_out,
+                              float alpha, float beta);
+int mpg_sell_cheb_sweep_f16f32(mpg_ctx_t ctx, mpg_sell_t A, const int8_t* row_exp, const float* dinv, const float* r,
+                               const float* z_in, const float* z_prev, float* z_out, float alpha, float beta);
+int mpg_csr_poly_sweep_f16f32(mpg_ctx_t ctx, mpg_csr_t A, const uint16_t* vals_half, const int8_t* row_exp,
+                              const float* dinv, const float* g, const float* p, float* z, float* out, int32_t form,
+                              int32_t first, int32_t last, float c0, float c1);
+int mpg_sell_poly_sweep_f16f32(mpg_ctx_t ctx, mpg_sell_t A, const int8_t* row_exp, const float* dinv, const float* g,
+                               const float* p, float* z, float* out, int32_t form, int32_t first, int32_t last,
+                               float c0, float c1);
+/* The values those entries compute with, as fp32 (a form of mpg_csr_half_values'
+ * inverse): out_f32[j] = float(half(vals_half[j])) 2^-row_exp[i] for entry j of
+ * row i (out_f32 NULL: nothing is stored). *nonfinite_host = the entries whose
+ * fp32 value is not finite (a row scaled down from beyond fp32's range).
+ * Set-up only: it waits for the context's stream. */
+int mpg_csr_half_dequant_f32(mpg_ctx_t ctx, mpg_csr_t A, const uint16_t* vals_half, const int8_t* row_exp,
+                             float* out_f32, int64_t* nonfinite_host);
+
 /* ---- the initial-guess store's kernels (an addition to the reference's set; mpg_engine_guess_*, solve.h) ----
  * fp64 throughout. A panel is column-major with leading dimension ld >= n, ld even, its base 16-byte aligned, and
  * holds nc <= MPG_GUESS_MAX_DEPTH columns; every vector is 16-byte aligned. Sums are two-stage and deterministic:

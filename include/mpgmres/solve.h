@@ -360,6 +360,18 @@ int mpg_engine_accum(mpg_engine_t e);
  * node blocks, a row-partitioned engine, the operator-surface engine, f16emu on SELL -- is MPG_ERR_UNSUPPORTED with
  * the reason in the message. f16emu: the same values held as fp32, for tests. */
 int mpg_engine_basis(mpg_engine_t e);
+/* The matrix values the sweeps of MPG_PREC_NEUMANN (jacobi_steps >= 2), MPG_PREC_CHEBYSHEV and MPG_PREC_GMRES_POLY read:
+ * MPG_PREC_VALUES_F32 0 / MPG_PREC_VALUES_F16 1 / MPG_PREC_VALUES_F16EMU 2 (mpg_arnoldi_set_prec_copy, arnoldi.h). Chosen
+ * by the setting MPG_PREC_VALUES = f32 (default: the Arnoldi matrix itself, nothing allocated, no launch changed) / f16 /
+ * f16emu, read once when the engine is created (any other value: MPG_ERR_ARG naming it). f16: the sweeps read A^ =
+ * mpg_csr_half_values(A, scale = 1), 2 bytes per value and one int8 exponent per row, as an MPG_F16 SELL copy where the
+ * Arnoldi SpMV runs on a SELL copy and in CSR order otherwise; the Arnoldi SpMV, the residual, Jacobi's diagonal, the
+ * Chebyshev interval and the GMRES-polynomial roots stay on the fp32 and fp64 values. Values that do not fit (fp16 after
+ * the row scaling, the int8 exponent, fp32 once unscaled) are MPG_ERR_RANGE at create and at mpg_engine_refresh_values,
+ * where the engine keeps its matrix. It runs on the fused engine on one GPU in mode mixed; a preconditioner without
+ * sweeps, another mode, a row-partitioned engine, the operator-surface engine and f16emu on SELL or node-block storage
+ * are MPG_ERR_UNSUPPORTED with the reason in the message. f16emu: A^ held as fp32 values on CSR row blocks, for tests. */
+int mpg_engine_prec_values(mpg_engine_t e);
 /* the residual prologue's storage (mpg_arnoldi_prologue_format: 1 CSR, 2 SELL, 3 node blocks) */
 int mpg_engine_prologue_format(mpg_engine_t e);
 /* ranks of the engine's communicator as its transport reports them: 1 for a
